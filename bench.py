@@ -8,13 +8,26 @@ compress_ratio 0.2, r 4, inputs resident in HBM.  At world size > 1 a bucket's p
 all-reduce and decode overlap the next bucket's encode.
 
     python bench.py [--gpus N --steps K --warmup W --ef ef14|ef21|noef --workload W]
+    python bench.py --full ...                      # every further leg, see below
+    python bench.py --dump-outputs DIR ...          # the last timed step's results as .npy
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
 Prints ONE JSON line (rank 0).  ``value`` = bucket bytes processed by all ranks
-/ wall time of the K timed steps (max over ranks).  ``roofline`` prices the
-dominant kernel (encode) by its algorithmic HBM bytes over its HIP-event
-duration; ``cpu_baseline`` times the CPU oracle (test infrastructure) on a
-bounded sample of the same bucket on this host.
+/ wall time of the K timed steps (max over ranks); ``ms_per_step`` = that wall time / K.
+A plain run does only this: set-up, warm-up, the K timed steps, the dump, the line.
+
+``--full`` adds the legs that take runs of their own (each can still be switched off by its
+``--no-...`` option): ``forced_exchange`` and ``emulated_wire`` time the N > 1 code path at
+N = 1, the marker pass gives ``phase_ms`` and ``roofline`` (the dominant kernel, encode,
+priced by its algorithmic HBM bytes over its HIP-event duration), and ``cpu_baseline``
+times the CPU oracle (test infrastructure) on the same bucket on this host.  Without
+``--full`` those fields are null.
+
+``--dump-outputs DIR`` writes, right after the timed steps, what the last of them returned:
+every bucket's decoded buffer (``out_b<i>.npy``) and the residuals it left (``residual_b<i>.npy``,
+``global_residual_b<i>.npy``) as float32, a fixed seeded sample of each array past the size cap,
+and ``<name>_sums.npy`` (float64: sum, sum of magnitudes, non-zero count over the whole array).
+The inputs are seeded, so two builds given the same arguments can be compared file by file.
 """
 from __future__ import annotations
 
@@ -163,6 +176,34 @@ def pmc_traffic(workload: str, ef: str, kernel: str, n_gpus: int = 1):
     return ent["bytes_per_launch"], os.path.relpath(paths[-1], REPO), match
 
 
+DUMP_TOTAL_BYTES = 48 << 20  # cap of one dump (float32 samples; the sums files are 24 B each)
+DUMP_SAMPLE = 1 << 20       # elements kept of an array larger than this
+
+
+def dump_outputs(dirname: str, arrays) -> dict:
+    """Write (name, tensor) pairs as dirname/<name>.npy (float32) and dirname/<name>_sums.npy.
+
+    An array with more elements than the cap is sampled at sorted indices drawn on the CPU from
+    a generator seeded by the array's position, so the same arguments give the same indices."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    cap = max(1, min(DUMP_SAMPLE, DUMP_TOTAL_BYTES // 4 // max(1, len(arrays))))
+    written = {}
+    for i, (name, t) in enumerate(arrays):
+        flat = t.detach().reshape(-1)
+        n = flat.numel()
+        sums = torch.stack([flat.sum(dtype=torch.float64), flat.abs().sum(dtype=torch.float64),
+                            torch.count_nonzero(flat).to(torch.float64)])
+        if n > cap:
+            g = torch.Generator().manual_seed(77_000 + i)
+            idx = torch.randint(n, (cap,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        np.save(os.path.join(dirname, name + ".npy"), flat.to(torch.float32).cpu().numpy())
+        np.save(os.path.join(dirname, name + "_sums.npy"), sums.cpu().numpy())
+        written[name] = {"elements": n, "saved": int(flat.numel())}
+    return written
+
+
 def _cpu_model() -> str:
     try:
         with open("/proc/cpuinfo") as fh:
@@ -289,6 +330,12 @@ def main():
                     help="bucket dtype (f32: every BASELINE config; bf16: the Llama driver's default)")
     ap.add_argument("--ratio", type=float, default=0.2)
     ap.add_argument("--r", type=int, default=4)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline figure: forced exchange, emulated "
+                         "wire, the marker pass (phase_ms, roofline) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them returned (every "
+                         "bucket's output and residuals) as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=8.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-phase-events", action="store_true")
@@ -375,8 +422,8 @@ def main():
 
     def step():
         futs = [hook(st, bk) for bk in buckets]
-        for f in futs:  # DDP's finalize: the caller's stream waits for every bucket's future
-            f.wait()
+        # DDP's finalize: the caller's stream waits for every bucket's future
+        return [f.wait() for f in futs]
 
     # warm-up (EF14: first call creates E; EF21: first call is the dense init)
     for _ in range(max(args.warmup, 2 if args.ef == "ef21" else 1)):
@@ -395,14 +442,24 @@ def main():
     dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    results = None
     for _ in range(args.steps):
-        step()
+        results = step()
     torch.cuda.synchronize()
     dist.barrier()
     elapsed = time.perf_counter() - t0
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+    dumped = None
+    if args.dump_outputs and rank == 0 and results is not None:
+        # before any further leg: they step the same buckets and residuals on
+        arrays = [(f"out_b{i}", t) for i, t in enumerate(results)]
+        for attr, tag in (("error_dict", "residual"), ("global_error_dict", "global_residual")):
+            for i, t in sorted((getattr(st, attr, None) or {}).items()):
+                if torch.is_tensor(t):
+                    arrays.append((f"{tag}_b{i}", t))
+        dumped = dump_outputs(args.dump_outputs, arrays)
     host_times = dict(_G.HOST_TIMES) if _G.HOST_TIMES is not None else None
     native_parts = None
     if native_ht is not None:
@@ -415,8 +472,8 @@ def main():
     # communicators, packed all-reduce on the exchange stream, deferred decodes) is timed
     # beside it in the same run, so the N = 1 point of a scaling run can be read on either.
     forced = None
-    if (world == 1 and args.hook == "arc" and not args.host_staged and not args.force_exchange
-            and not args.no_forced_exchange and args.backend == "nccl"):
+    if (args.full and world == 1 and args.hook == "arc" and not args.host_staged
+            and not args.force_exchange and not args.no_forced_exchange and args.backend == "nccl"):
         st.force_exchange = True
         st.init_exchange_comms(dev)
         for _ in range(2):
@@ -454,8 +511,8 @@ def main():
     # read and rewritten in HBM by WIRE_BLOCKS workgroups, paced to the bus bandwidth -- so the
     # codec's kernels run beside the collective's CU and HBM footprint.
     wire = []
-    if (world == 1 and args.hook == "arc" and not args.host_staged and not args.force_exchange
-            and args.backend == "nccl"):
+    if (args.full and world == 1 and args.hook == "arc" and not args.host_staged
+            and not args.force_exchange and args.backend == "nccl"):
         for bw in args.wire_busbw or []:
             st.reset_exchange_comms()
             st.emulate_wire = dict(ranks=args.wire_ranks, busbw_gbs=bw, latency_us=15.0, blocks=args.wire_blocks)
@@ -491,7 +548,7 @@ def main():
     phase_ms = {}
     light = {}
     sample_steps = 0
-    if not args.no_phase_events and args.hook == "arc":
+    if args.full and not args.no_phase_events and args.hook == "arc":
         # a separate marker pass (not in `value`): device-scope HIP events recorded by the native
         # step itself on the streams the kernels run on.  Each marker between two kernels idles
         # the GPU a few us, so they are sparse: on every 2nd call alternately a marker after the
@@ -610,6 +667,7 @@ def main():
         "metric": METRIC, "value": round(value, 2), "unit": "GB/s", "n_gpus": world,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype,
+        "full": args.full, "dumped_outputs": dumped,
         "data": "synthetic (N(0,1) fp32 gradients, per-rank seed)",
         "config": {"workload": f"{'arctopk' if args.hook == 'arc' else args.hook}_{args.ef}_{nb}x_{label}"
                                + ("_as_bf16" if args.dtype == "bf16" else "")
@@ -633,7 +691,7 @@ def main():
         "phase_ms_note": "separate pass, every call marked, decodes inline (not deferred)" if phase_ms else None,
         "roofline": roof,
         "algorithmic_bytes_per_call": {k: int(v) for k, v in alg.items()},
-        "cpu_baseline": None if world == 1 else {
+        "cpu_baseline": None if world == 1 or not args.full else {
             "value": None, "unit": "GB/s", "cores": 0, "kind": "port",
             "sample": "not timed at N > 1: the CPU baseline runs on rank 0 of the N = 1 line only "
                       "(bench contract); see that line's cpu_baseline (ws 1 and ws 2 over gloo)"},
@@ -641,7 +699,7 @@ def main():
     if world > 1:
         out["value_semantics"] = (f"value = bucket bytes of all {world} ranks / wall time (whole-job "
                                   f"aggregate, bench contract); per_gpu_value = value / {world}")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.ef, args.cpu_seconds, args.workload, label,
                                            eb * bucket_numel(shapes), args.hook)
     if host_times is not None and rank == 0:  # ARCTOPK_HOST_TIMING=1: host us per hook call

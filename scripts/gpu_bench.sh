@@ -14,7 +14,7 @@ i=0
 while read -r args; do
   case "$args" in ''|'#'*) continue ;; esac
   i=$((i+1))
-  timeout -k 10 ${RUN_LIMIT:-240} python bench.py $args > "$OUT/w$i.log" 2>&1 || {
+  timeout -k 10 ${RUN_LIMIT:-240} python bench.py --full $args > "$OUT/w$i.log" 2>&1 || {
     echo "bench [$args] failed rc=$?"; tail -20 "$OUT/w$i.log"; exit 1; }
   tail -1 "$OUT/w$i.log" >> "$OUT/wl.jsonl"
   echo "[$args] done"

@@ -53,6 +53,32 @@ def test_bench_refuses_a_world_size_mismatch():
     assert r.returncode != 0 and "WORLD_SIZE=1" in r.stderr
 
 
+def test_dump_outputs_writes_a_fixed_sample_and_whole_array_sums(tmp_path):
+    """--dump-outputs: float32 files, an array past the cap sampled at the same sorted indices on
+    every call, a small one whole, and float64 sums over the whole array beside each."""
+    import numpy as np
+    import torch
+    big = torch.arange(bench.DUMP_SAMPLE + 12345, dtype=torch.float32)
+    small = torch.tensor([1.5, -2.0, 0.0, 4.0], dtype=torch.bfloat16)
+    for d in ("a", "b"):
+        info = bench.dump_outputs(str(tmp_path / d), [("out_b0", big), ("residual_b0", small)])
+        assert info == {"out_b0": {"elements": big.numel(), "saved": bench.DUMP_SAMPLE},
+                        "residual_b0": {"elements": 4, "saved": 4}}
+    a, b = np.load(tmp_path / "a" / "out_b0.npy"), np.load(tmp_path / "b" / "out_b0.npy")
+    assert a.dtype == np.float32 and a.shape == (bench.DUMP_SAMPLE,) and np.array_equal(a, b)
+    assert np.all(np.diff(a) >= 0) and len(np.unique(a)) > bench.DUMP_SAMPLE // 2  # spread, in order
+    s = np.load(tmp_path / "a" / "residual_b0.npy")
+    assert s.dtype == np.float32 and s.tolist() == [1.5, -2.0, 0.0, 4.0]
+    sums = np.load(tmp_path / "a" / "residual_b0_sums.npy")
+    assert sums.dtype == np.float64 and sums.tolist() == [3.5, 7.5, 3.0]
+    n = big.numel()
+    assert np.load(tmp_path / "a" / "out_b0_sums.npy").tolist() == [n * (n - 1) / 2, n * (n - 1) / 2, n - 1]
+    # many arrays share the dump's size cap
+    many = [(f"out_b{i}", big) for i in range(24)]
+    bench.dump_outputs(str(tmp_path / "c"), many)
+    assert sum(os.path.getsize(tmp_path / "c" / f) for f in os.listdir(tmp_path / "c")) <= 64 * 10**6
+
+
 def test_sparse_algorithmic_bytes_follow_the_survey_formula():
     n, k = 67_108_864, 13_421_760
     assert bench.sparse_algorithmic_bytes("topk", "ef14", n, k, 1) == 28 * n + 24 * k
