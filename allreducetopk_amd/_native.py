@@ -109,6 +109,12 @@ _SIGS = {
     "arctopk_randk_select_ef14": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, POINTER(c_int64),
                                             POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), c_uint64,
                                             c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
+    "arctopk_seg_workspace_bytes": (c_int64, [c_int32, POINTER(c_int64), POINTER(c_int64),
+                                              POINTER(c_int64), c_int32]),
+    "arctopk_seg_select": (c_int32, [c_void_p, c_int32, POINTER(c_int64), POINTER(c_int64),
+                                     POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), c_int32,
+                                     c_int32, c_uint64, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
+                                     c_void_p]),
     "arctopk_sparse_gather": (c_int32, [c_void_p, c_int32, POINTER(c_int64), POINTER(c_int64),
                                         POINTER(c_int64), c_void_p, c_void_p, c_int32, c_void_p]),
     "arctopk_sparse_residual": (c_int32, [c_void_p, c_int32, POINTER(c_int64), POINTER(c_int64),

@@ -21,8 +21,23 @@ Per bucket call (all on the caller's stream, no host synchronisation):
                                            -> decode: zero + rank-ordered scatter-add, / ws
     EF21: gE += out; out = gE (fused into decode)
 
-Only ``sparse_type="tensor"`` works in the reference (row/column unpack 2 values
-where 3 are expected, :54, :75, :96); the same types raise here.
+``sparse_type`` "row" / "column" (the reference's sparsify_by_row / sparsify_by_column, :36-75,
+which its hook cannot reach: 2 values are unpacked where 3 are expected, :54, :75, :96) select per
+row / per column of every tensor with the segmented select (arctopk_seg_select):
+
+    2-D [R, C]   row: every row takes max(1, int(C * ratio)) entries; column: every column takes
+                 max(1, int(R * ratio)) entries (cal_k_by_row / cal_k_by_column)
+    1-D          one segment: exactly what "tensor" does (a RandK state draws RandK here too; the
+                 reference forgets to forward ``random`` for 1-D tensors)
+    N-D, N >= 3  viewed as [shape[0], numel / shape[0]] (the reference's ``num_rows, num_cols =
+                 tensor.shape`` raises): a conv weight selects per output channel in row mode
+    payload      int32 flat indices into the tensor; row: segment-major, ascending; column: the
+                 reference's [k_seg, C] layout (entry j of column c at j * C + c)
+    RandK        "torch" / "host": one torch.randperm(C)[:k] per row (column: randperm(R)[:k] per
+                 column) in the reference's order; "hash": per segment s of tensor t the k largest
+                 keys rk(hseed(t, s), j) (include/arctopk.h)
+    EF14         arctopk_ef14_fold, then the select on E with the selected elements zeroed
+
 Ties at the k-th |x| resolve lowest-index first.
 """
 
@@ -40,12 +55,40 @@ from allreducetopk_amd.comm_hooks.utils import (HookState, _get_allgather_out_li
 
 logger = logging.getLogger(__name__)
 
-__all__ = ["SparseState", "sparse_hook_sync", "cal_k"]
+__all__ = ["SparseState", "sparse_hook_sync", "cal_k", "cal_k_by_row", "cal_k_by_column"]
 
 
 def cal_k(tensor, compress_ratio):
     """k of a tensor (ref sparse_hook.py:77-78)."""
     return max(1, int(tensor.numel() * compress_ratio))
+
+
+def _view_2d(shape):
+    """(rows, cols) of a tensor for row / column selection; None for one segment (<= 1-D).
+    N-D tensors are viewed as [shape[0], numel / shape[0]]."""
+    if len(shape) <= 1:
+        return None
+    n = 1
+    for d in shape:
+        n *= int(d)
+    rows = int(shape[0])
+    return rows, n // max(rows, 1)
+
+
+def cal_k_by_row(tensor, compress_ratio):
+    """Entries of a tensor under sparse_type="row" (ref sparse_hook.py:80-84; N-D: per shape[0])."""
+    v = _view_2d(tensor.shape)
+    if v is None:
+        return cal_k(tensor, compress_ratio)
+    return max(1, int(v[1] * compress_ratio)) * v[0]
+
+
+def cal_k_by_column(tensor, compress_ratio):
+    """Entries of a tensor under sparse_type="column" (ref sparse_hook.py:86-90; N-D as above)."""
+    v = _view_2d(tensor.shape)
+    if v is None:
+        return cal_k(tensor, compress_ratio)
+    return max(1, int(v[0] * compress_ratio)) * v[1]
 
 
 class SparseState(HookState):
@@ -77,6 +120,7 @@ class SparseState(HookState):
         self.index_source = index_source
         self._workspace = None
         self._ws_bytes: Dict[tuple, int] = {}
+        self._seg_geom: Dict[tuple, "_SegGeometry"] = {}  # row / column: per bucket layout and ratio
         self._fold_in = None  # RandK "hash" under EF14: the select applies E (1) or the first-call copy (2)
 
     # ratio of this call; the c4 variant overrides (gradual compression)
@@ -101,6 +145,65 @@ def _workspace(state, device, numels) -> torch.Tensor:
         ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
         state._workspace = ws
     return ws
+
+
+class _SegGeometry:
+    """Row / column geometry of one bucket layout at one ratio: per tensor the [rows, cols] view,
+    the entries per segment, the tensor's total (``ks``) and its offset in the payload."""
+
+    def __init__(self, shapes, ratio: float, by_column: bool):
+        self.by_column = by_column
+        self.rows, self.cols, self.k_seg, self.ks, self.k_off = [], [], [], [], []
+        acc = 0
+        for shape in shapes:
+            v = _view_2d(shape)
+            if v is None:  # one segment; a column of n rows is the same contiguous segment
+                n = int(shape[0]) if len(shape) else 1
+                r, c = (n, 1) if by_column else (1, n)
+            else:
+                r, c = v
+            seg_len, nseg = (r, c) if by_column else (c, r)
+            k = max(1, int(seg_len * ratio))
+            self.rows.append(r)
+            self.cols.append(c)
+            self.k_seg.append(k)
+            self.ks.append(k * nseg)
+            self.k_off.append(acc)
+            acc += k * nseg
+        self.sum_k = acc
+        self.a_rows, self.a_cols, self.a_kseg = (N.i64_array(self.rows), N.i64_array(self.cols),
+                                                 N.i64_array(self.k_seg))
+        self.ws_bytes = int(N.lib().arctopk_seg_workspace_bytes(len(self.rows), self.a_rows, self.a_cols,
+                                                                self.a_kseg, int(by_column)))
+        if self.ws_bytes < 0:
+            N.check(-self.ws_bytes, "arctopk_seg_workspace_bytes")
+
+
+def _seg_geometry(state, tensors, ratio: float) -> _SegGeometry:
+    key = (tuple(tuple(t.shape) for t in tensors), float(ratio), state.sparse_type)
+    g = state._seg_geom.get(key)
+    if g is None:
+        g = state._seg_geom[key] = _SegGeometry(key[0], ratio, state.sparse_type == "column")
+    return g
+
+
+def _seg_reference_draws(g: _SegGeometry, device) -> torch.Tensor:
+    """RandK "torch" / "host" under row / column: the reference's draws in its order
+    (sparsify_by_row :46, sparsify_by_column :66, sparsify :20), as int32 flat indices.
+    device None: the CPU generator."""
+    kw = {} if device is None else {"device": device}
+    parts = []
+    for r, c, k in zip(g.rows, g.cols, g.k_seg):
+        if g.by_column and c > 1:
+            idx = torch.stack([torch.randperm(r, **kw)[:k] for _ in range(c)], dim=1)
+            idx = idx * c + torch.arange(c, **kw).unsqueeze(0)
+        elif not g.by_column and r > 1:
+            idx = torch.stack([torch.randperm(c, **kw)[:k] for _ in range(r)], dim=0)
+            idx = idx + torch.arange(r, **kw).unsqueeze(1) * c
+        else:
+            idx = torch.randperm(r * c, **kw)[:k]
+        parts.append(idx.flatten().to(torch.int32))
+    return torch.cat(parts)
 
 
 def _sparse_hook_impl(state: SparseState, bucket, c4: bool = False) -> "torch.futures.Future[torch.Tensor]":
@@ -141,7 +244,7 @@ def _sparse_hook_impl(state: SparseState, bucket, c4: bool = False) -> "torch.fu
         # from E, and the decode writes the bucket once.  RandK's device draw folds E itself in
         # its write pass (arctopk_randk_select_ef14: its keys never read the data)
         # (and fp32 TopK folds it in its first pass: arctopk_topk_select_ef14)
-        if not _select_folds(state, dtype):
+        if not _select_folds(state, dtype) or state.sparse_type != "tensor":
             N.check(L.arctopk_ef14_fold(input_tensor.data_ptr(), err.data_ptr(), total, int(err_in),
                                         dt, stream), "arctopk_ef14_fold")
         state._fold_in = int(err_in)
@@ -162,14 +265,14 @@ def _sparse_hook_impl(state: SparseState, bucket, c4: bool = False) -> "torch.fu
             fut.set_result(input_tensor)
             return fut
 
-    if ef != N.EF14 or not _select_folds(state, dtype):
+    if ef != N.EF14 or not _select_folds(state, dtype) or state.sparse_type != "tensor":
         state._fold_in = None  # (set above only when the select folds E itself)
     seed = None
     if state.random:  # shared reseed so every rank draws the same indices (:230-235)
         seed = torch.randint(0, 1_000_000_000, (1,), generator=state.rng).item()
         torch.manual_seed(seed)
     _compress_exchange(state, bucket, group, world_size, ef, state._call_ratio(), seed,
-                       e_decay=decay, g_decay=decay, count_bits=True)
+                       e_decay=decay, g_decay=decay, count_bits=True, ef14_folded=ef == N.EF14)
     state.maybe_increase_iter(bucket)
     fut = torch.futures.Future()
     fut.set_result(input_tensor)
@@ -185,19 +288,22 @@ def _select_folds(state: SparseState, dtype) -> bool:
 
 
 def _check_compressible(state: SparseState, input_tensor: torch.Tensor) -> None:
-    if state.sparse_type != "tensor":  # the reference crashes for row/column (:96)
-        raise ValueError(f"not enough values to unpack (sparse_type={state.sparse_type!r}: only "
-                         "'tensor' is functional in the reference)")
+    if state.sparse_type not in ("tensor", "row", "column"):
+        raise ValueError(f"sparse_type must be 'tensor', 'row' or 'column', not {state.sparse_type!r}")
     if not input_tensor.is_cuda or input_tensor.dtype not in N.DTYPE_CODE:
         raise RuntimeError("sparse HIP codec needs a float32 or bfloat16 bucket on a GPU")
 
 
 def _compress_exchange(state: SparseState, bucket, group, world_size: int, ef: int, ratio: float,
-                       seed, e_decay: float, g_decay: float, count_bits: bool, on_values=None) -> None:
+                       seed, e_decay: float, g_decay: float, count_bits: bool, on_values=None,
+                       ef14_folded: bool = False) -> None:
     """The compressed call after the EF pre-apply, on the caller's stream: select (TopK) or draw
     (RandK) the indices, gather the values, persist the residual (EF14: E[idx] = 0; EF21:
     E[idx] += e_decay * values), exchange (RandK: all-reduce; TopK: all-gather of values and
     indices) and decode into the bucket (EF21: gE += g_decay * out, out = gE).
+    ``sparse_type`` "row" / "column": the per-segment select (arctopk_seg_select) with the tensors'
+    totals as ``ks``; under EF14 the caller has folded E := G + E already and says so with
+    ``ef14_folded`` (the tensor path's fused folds go by ``state._fold_in`` as before).
     Reference: sparse_hook.py:237-297 (and :363-410 for the large-batch hook)."""
     L = N.lib()
     input_tensor = bucket.buffer()
@@ -209,7 +315,9 @@ def _compress_exchange(state: SparseState, bucket, group, world_size: int, ef: i
     stream = torch.cuda.current_stream(device).cuda_stream
     dt = N.DTYPE_CODE[dtype]
     numels = [t.numel() for t in tensors]
-    ks = [max(1, int(n * ratio)) for n in numels]
+    # row / column: per-segment selection; ks are then the per-tensor totals
+    seg = _seg_geometry(state, tensors, ratio) if state.sparse_type != "tensor" else None
+    ks = seg.ks if seg is not None else [max(1, int(n * ratio)) for n in numels]
     offsets: List[int] = []
     off = 0
     for t in tensors:
@@ -231,7 +339,24 @@ def _compress_exchange(state: SparseState, bucket, group, world_size: int, ef: i
     indices = torch.empty(sum_k, dtype=torch.int32, device=device)
     x = input_tensor.data_ptr()
     xsrc = state.error_dict[b].data_ptr() if fold14 else x
-    if state.random:
+    if seg is not None:
+        if fold14 and not ef14_folded:
+            raise RuntimeError("row / column selection under EF14 needs the caller's arctopk_ef14_fold")
+        hashed = state.random and state.index_source == "hash"
+        if state.random and not hashed:  # the reference's own draws, then the gather
+            indices.copy_(_seg_reference_draws(seg, device if state.index_source == "torch" else None))
+            N.check(L.arctopk_sparse_gather(xsrc, nt, a_off, a_k, a_ko, indices.data_ptr(),
+                                            values.data_ptr(), dt, stream), "arctopk_sparse_gather")
+        else:  # EF14's `E[indices] = 0` (:104) happens in the select's write pass
+            ws = state._workspace
+            if ws is None or ws.device != device or ws.numel() < seg.ws_bytes:
+                ws = state._workspace = torch.empty(seg.ws_bytes, dtype=torch.uint8, device=device)
+            N.check(L.arctopk_seg_select(xsrc, nt, a_off, seg.a_rows, seg.a_cols, seg.a_kseg, a_ko,
+                                         int(seg.by_column), int(hashed), int(seed) if hashed else 0,
+                                         indices.data_ptr(), values.data_ptr(), ws.data_ptr(), dt,
+                                         int(fold14), stream), "arctopk_seg_select")
+        bits_sum = sum_k * (dtype_bits(dtype) + (0 if state.random else 32))
+    elif state.random:
         if state.index_source == "torch":  # the reference's own draw (:20), per tensor in order
             for t, k, ko in zip(tensors, ks, k_off):
                 indices[ko:ko + k].copy_(torch.randperm(t.numel(), device=device)[:k])
@@ -294,7 +419,8 @@ def _compress_exchange(state: SparseState, bucket, group, world_size: int, ef: i
             state.comm_bits_this_round += 2 * (world_size - 1) * bits_sum
         if world_size > 1:
             dist.all_reduce(values, group=group, async_op=False)
-        ascending = 2 if state.index_source == "hash" else 0  # one pass of whole chunks
+        # one pass of whole chunks where every tensor's indices ascend (not the column layout)
+        ascending = 2 if state.index_source == "hash" and not (seg is not None and seg.by_column) else 0
         N.check(L.arctopk_sparse_decode(x, total, nt, a_off, a_k, a_ko, sum_k, indices.data_ptr(),
                                         values.data_ptr(), 1, world_size, ascending, gerr, g_decay, dt,
                                         stream),
@@ -310,7 +436,8 @@ def _compress_exchange(state: SparseState, bucket, group, world_size: int, ef: i
         else:  # gathering from one rank is the identity
             all_vals, all_idx = values, indices
         N.check(L.arctopk_sparse_decode(x, total, nt, a_off, a_k, a_ko, sum_k, all_idx.data_ptr(),
-                                        all_vals.data_ptr(), world_size, world_size, 1, gerr,
+                                        all_vals.data_ptr(), world_size, world_size,
+                                        3 if seg is not None and seg.by_column else 1, gerr,
                                         g_decay, dt, stream), "arctopk_sparse_decode")
 
 

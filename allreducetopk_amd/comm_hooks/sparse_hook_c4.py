@@ -17,7 +17,7 @@ from allreducetopk_amd.comm_hooks import sparse_hook as _base
 
 logger = logging.getLogger(__name__)
 
-__all__ = ["SparseState", "sparse_hook_sync", "cal_k"]
+__all__ = ["SparseState", "sparse_hook_sync", "cal_k", "cal_k_by_row", "cal_k_by_column"]
 
 
 class SparseState(_base.SparseState):
@@ -54,6 +54,11 @@ class SparseState(_base.SparseState):
             self.compression_started = True
             logger.info("Starting compression at iteration %s with gradual compression enabled: %s",
                         self.iter, self.gradual_compression)
+
+
+# (tensor, compress_ratio), as the reference's sparse_hook_c4.py:83-90
+cal_k_by_row = _base.cal_k_by_row
+cal_k_by_column = _base.cal_k_by_column
 
 
 def cal_k(state, tensor):

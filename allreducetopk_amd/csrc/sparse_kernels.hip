@@ -397,7 +397,9 @@ int sparse_decode_t(T* out, int64_t numel, int32_t nt, const int64_t* offsets, c
                     hipStream_t st) {
     // TopK (accumulate 1) and RandK with ascending indices (accumulate 2): the first payload
     // writes the whole bucket, zeros included (k_scatter_first); the tensors tile the bucket in order
-    bool tiled = accumulate != 0;
+    // (accumulate 3: TopK payloads in no particular order -- memset, then the rank-ordered scatters)
+    bool tiled = accumulate == 1 || accumulate == 2;
+    const bool ranked = accumulate == 1 || accumulate == 3;
     for (int32_t i = 0; tiled && i < nt; ++i) {
         const int64_t end = i + 1 < nt ? offsets[i + 1] : numel;
         if (offsets[i] < 0 || end <= offsets[i] || end - offsets[i] >= (1ll << 31) || (i == 0 && offsets[0] != 0))
@@ -424,7 +426,7 @@ int sparse_decode_t(T* out, int64_t numel, int32_t nt, const int64_t* offsets, c
         }
     }
     const float wsf = (float)world_size;
-    const int nr = accumulate == 1 ? nranks : 1;
+    const int nr = ranked ? nranks : 1;
     for (int q = tiled ? 1 : 0; q < nr; ++q) {
         for (int32_t first = 0; first < nt; first += kB) {
             SparseBatch b;
@@ -435,16 +437,16 @@ int sparse_decode_t(T* out, int64_t numel, int32_t nt, const int64_t* offsets, c
             dim3 grid(grid_for(maxk, 2048), cnt);
             const int32_t* iq = idx + (int64_t)q * packed_len;
             const T* vq = vals + (int64_t)q * packed_len;
-            if (accumulate == 1 && q > 0)
+            if (ranked && q > 0)
                 hipLaunchKernelGGL((k_scatter<T, 1>), grid, dim3(256), 0, st, b, out, iq, vq, wsf);
-            else if (accumulate == 1)
+            else if (ranked)
                 hipLaunchKernelGGL((k_scatter<T, 2>), grid, dim3(256), 0, st, b, out, iq, vq, wsf);
             else
                 hipLaunchKernelGGL((k_scatter<T, 0>), grid, dim3(256), 0, st, b, out, iq, vq, wsf);
         }
     }
     // TopK's out /= ws (sparse_hook.py:293) is the identity at ws = 1 (x / 1 == x for every x)
-    const bool div = accumulate == 1 && world_size > 1;
+    const bool div = ranked && world_size > 1;
     if (div || gerr) {
         hipLaunchKernelGGL(k_div_gE<T>, dim3(grid_for(numel, 8192)), dim3(256), 0, st, out, gerr,
                            numel, wsf, div ? 1 : 0, decay);
@@ -459,7 +461,7 @@ extern "C" int arctopk_sparse_decode(void* out, int64_t numel, int32_t nt, const
                                      int32_t world_size, int32_t accumulate, void* gerr,
                                      float decay, int32_t dtype, void* stream) {
     if (!out || !offsets || !ks || !k_off || !idx || !vals || nt < 1 || nranks < 1 ||
-        world_size < 1 || numel < 0 || accumulate < 0 || accumulate > 2)
+        world_size < 1 || numel < 0 || accumulate < 0 || accumulate > 3)
         return ARCTOPK_EINVAL;
     if (dtype != ARCTOPK_F32 && dtype != ARCTOPK_BF16) return ARCTOPK_EINVAL;
     hipStream_t st = (hipStream_t)stream;

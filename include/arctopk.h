@@ -448,6 +448,38 @@ int arctopk_randk_select_ef14(const void* g, void* E, int32_t err_in, int32_t nt
                               const int64_t* k_off, uint64_t seed, int32_t* idx, void* vals,
                               void* workspace, int32_t dtype, void* stream);
 
+/*
+ * Row- and column-wise selection (sparse_type "row" / "column": sparsify_by_row, sparsify_by_column,
+ * sparse_hook.py:36-75).  Tensor i is viewed as [rows[i], cols[i]] (row-major at offsets[i]);
+ * by_column = 0: every row is a segment of cols[i] contiguous elements; by_column = 1: every column
+ * is a segment of rows[i] elements at stride cols[i].  Each segment takes its own k_seg[i] keys
+ * (1 <= k_seg <= segment length), so tensor i has nseg * k_seg[i] entries from k_off[i] on.
+ *   hashed = 0 (TopK): the k_seg largest |x| of the segment, ties at the threshold lowest position
+ *     in the segment first.
+ *   hashed = 1 (RandK): the k_seg largest keys rk(hseed(i, s), j) over the positions j of segment s
+ *     (rk: arctopk_randk_select's keyed bijection), with
+ *     hseed(i, s) = low32(fin(seed + 0x9E3779B97F4A7C15 * (i + 1) + 0xD1B54A32D192ED03 * s)) mod 2^64,
+ *     fin the splitmix64 finaliser; hseed(i, 0) is arctopk_randk_select's seed of tensor i, so a
+ *     one-segment tensor draws what that entry draws.
+ * idx holds int32 flat indices into the tensor (row * cols + column):
+ *   by_column = 0: segment-major, ascending within a segment -- ascending over the tensor;
+ *   by_column = 1: the reference's [k_seg, cols] layout: entry j of column c is at
+ *     k_off[i] + j * cols + c and holds row_j(c) * cols + c with row_0(c) < row_1(c) < ...
+ * x != NULL: vals = x[offsets[i] + idx] in the same layout, and with zero_selected x is written
+ * back with those elements zeroed in the same pass (EF14 on E); x = NULL needs hashed: indices
+ * only (offsets / vals NULL, zero_selected 0).  ARCTOPK_EINVAL, with nothing enqueued, for null
+ * arrays, rows * cols outside [1, 2^31), k_seg outside [1, segment length] or a bad dtype.
+ * Row segments longer than 12,288 keys go through the multi-block select of arctopk_topk_select
+ * (one item per segment); column strips re-read their keys from memory and have no row limit.
+ * workspace: arctopk_seg_workspace_bytes of the same geometry (-ARCTOPK_EINVAL for a bad one).
+ */
+int64_t arctopk_seg_workspace_bytes(int32_t ntensors, const int64_t* rows, const int64_t* cols,
+                                    const int64_t* k_seg, int32_t by_column);
+int arctopk_seg_select(void* x, int32_t ntensors, const int64_t* offsets, const int64_t* rows,
+                       const int64_t* cols, const int64_t* k_seg, const int64_t* k_off,
+                       int32_t by_column, int32_t hashed, uint64_t seed, int32_t* idx, void* vals,
+                       void* workspace, int32_t dtype, int32_t zero_selected, void* stream);
+
 /* Gather vals[k_off[i] + j] = x[offsets[i] + idx[k_off[i] + j]]  (sparse_hook.py:22). */
 int arctopk_sparse_gather(const void* x, int32_t ntensors, const int64_t* offsets,
                           const int64_t* ks, const int64_t* k_off, const int32_t* idx,
@@ -470,6 +502,8 @@ int arctopk_sparse_residual(void* E, int32_t ntensors, const int64_t* offsets,
  *                           pass of whole chunks (zeros and values composed in LDS)
  *   accumulate = 1 (TopK) : out = 0; for rank q = 0..nranks-1 in order:
  *                           out[off + idx_q[j]] += vals_q[j]; then out /= world_size (:285-292)
+ *   accumulate = 3 (TopK, idx in any order: arctopk_seg_select's column layout): the same sums
+ *                           in the same rank order, as a memset and one scatter per rank
  * `vals`/`idx` hold nranks consecutive payloads of packed_len entries each.
  * EF21 (gerr != NULL): gE = gE + decay * out (one rounding: gE.add_(out, alpha=error_decay));
  * out = gE (:295-297).
