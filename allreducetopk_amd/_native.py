@@ -20,7 +20,8 @@ LIB_PATH = LIB_OVERRIDE or os.path.join(PKG, "lib", "libarctopk.so")
 EF_NONE, EF14, EF21 = 0, 1, 2
 EF_CODE = {"noef": EF_NONE, "ef14": EF14, "ef21": EF21}
 EINVAL = 1001  # ARCTOPK_EINVAL
-SEG_RAW, SEG_SKETCH = 0, 1
+SEG_RAW, SEG_SKETCH, SEG_DENSE = 0, 1, 2
+PLAN_DENSE_1D, PLAN_RESTART_DRAWS = 1, 2  # ARCTOPK_PLAN_* flags (arctopk_plan_create_ex)
 F32 = 0
 BF16 = 1
 DTYPE_CODE = {torch.float32: F32, torch.bfloat16: BF16}  # bucket dtype -> ARCTOPK_F32 / _BF16
@@ -54,9 +55,13 @@ class Segment(ctypes.Structure):
 _SIGS = {
     "arctopk_plan_create": (c_int32, [POINTER(c_int64), POINTER(c_int32), c_int32, c_int32, c_double,
                                       c_int32, c_int32, POINTER(c_void_p)]),
+    "arctopk_plan_create_ex": (c_int32, [POINTER(c_int64), POINTER(c_int32), c_int32, c_int32, c_double,
+                                         c_int32, c_int32, c_int32, POINTER(c_void_p)]),
     "arctopk_plan_destroy": (c_int32, [c_void_p]),
     "arctopk_plan_describe": (c_int32, [POINTER(c_int64), POINTER(c_int32), c_int32, c_int32, c_double,
                                         c_void_p, POINTER(PlanInfo)]),
+    "arctopk_plan_describe_ex": (c_int32, [POINTER(c_int64), POINTER(c_int32), c_int32, c_int32, c_double,
+                                           c_int32, c_void_p, POINTER(PlanInfo)]),
     "arctopk_plan_query": (c_int32, [c_void_p, POINTER(PlanInfo)]),
     "arctopk_plan_group": (c_int32, [c_void_p, c_int32, c_int32, POINTER(c_void_p)]),
     "arctopk_plan_segment": (c_int32, [c_void_p, c_int32, POINTER(Segment)]),

@@ -108,7 +108,8 @@ def group_runs(segs, numel: int, esz: int, target_bytes: int):
 class BucketPlan:
     """Native plan + persistent device buffers of one bucket layout."""
 
-    def __init__(self, shapes: List[Tuple[int, ...]], r: int, ratio: float, dtype, device):
+    def __init__(self, shapes: List[Tuple[int, ...]], r: int, ratio: float, dtype, device,
+                 flags: int = 0):
         if dtype not in N.DTYPE_CODE:
             raise TypeError(f"ARC-TopK HIP codec supports float32 and bfloat16 buckets, got {dtype}")
         L = N.lib()
@@ -121,11 +122,17 @@ class BucketPlan:
         self.r = r
         self.ratio = ratio
         self.device = torch.device(device)
+        self.flags = int(flags)  # N.PLAN_* (the c4 hook: dense 1-D tensors, restarted draws)
         handle = N.c_void_p()
-        st = L.arctopk_plan_create((N.c_int64 * max(1, len(dims)))(*dims), (N.c_int32 * len(nd))(*nd),
-                                   len(nd), r, float(ratio), N.DTYPE_CODE[dtype], self.device.index or 0,
-                                   N.ctypes.byref(handle))
-        N.check(st, f"arctopk_plan_create(shapes={shapes}, r={r}, ratio={ratio})")
+        if self.flags:
+            st = L.arctopk_plan_create_ex((N.c_int64 * max(1, len(dims)))(*dims), (N.c_int32 * len(nd))(*nd),
+                                          len(nd), r, float(ratio), N.DTYPE_CODE[dtype],
+                                          self.device.index or 0, self.flags, N.ctypes.byref(handle))
+        else:
+            st = L.arctopk_plan_create((N.c_int64 * max(1, len(dims)))(*dims), (N.c_int32 * len(nd))(*nd),
+                                       len(nd), r, float(ratio), N.DTYPE_CODE[dtype], self.device.index or 0,
+                                       N.ctypes.byref(handle))
+        N.check(st, f"arctopk_plan_create(shapes={shapes}, r={r}, ratio={ratio}, flags={self.flags})")
         self.handle = handle
         info = N.PlanInfo()
         N.check(L.arctopk_plan_query(handle, N.ctypes.byref(info)), "arctopk_plan_query")
@@ -180,9 +187,10 @@ class BucketPlan:
                                     self.slotmap.data_ptr(), self.packed.data_ptr(),
                                     self.V_ring[0].data_ptr()), "arctopk_plan_bind")
         bits = dtype_bits(dtype)
-        # bits_sum of one call: sketch P + selected values per tensor (:32, :57, :70, :119)
-        self.bits_sum = sum(((s.n if s.kind == N.SEG_RAW else s.n * r) + s.k_rows * s.m) * bits
-                            for s in self.segments)
+        # bits_sum of one call: sketch P + selected values per tensor (:32, :57, :70, :119);
+        # a DENSE tensor has no sketch (P_bits 0) and sends its n values (c4 :22-23)
+        self.bits_sum = sum(((s.n * r if s.kind == N.SEG_SKETCH else s.n if s.kind == N.SEG_RAW else 0)
+                             + s.k_rows * s.m) * bits for s in self.segments)
 
     V_RING = 4        # projection slots allocated up front per bucket
     V_RING_MAX = 32   # ... and at most (then the copy stream waits for the oldest reader)
@@ -366,7 +374,10 @@ class GroupPlan:
         self.offset = int(s0.offset)  # first bucket element of the run
         vb = next((int(s.v_off) for s in parent.segments[seg_begin:seg_end] if s.kind == N.SEG_SKETCH), 0)
         self.v_off = vb
-        self.sketch = parent.sketch[int(s0.sketch_off):int(s0.sketch_off) + max(1, info.sketch_len)]
+        if info.sketch_len:
+            self.sketch = parent.sketch[int(s0.sketch_off):int(s0.sketch_off) + info.sketch_len]
+        else:  # DENSE segments only: no sketch is written or reduced; any address binds
+            self.sketch = parent.sketch[:1]
         self.packed = parent.packed[int(s0.packed_off):int(s0.packed_off) + max(1, info.packed_len)]
         self.rowlist = parent.rowlist[int(s0.sel_off):]
         self.slotmap = parent.slotmap[int(s0.row_off):]
@@ -667,21 +678,36 @@ class GroupTopKState(HookState):
             self._first_compressed_iter = self.iter
         # fast path: the bucket's flat buffer is the one this plan was built for (DDP keeps a
         # bucket's buffer across iterations; its one-time rebuild falls in the check window)
-        ident = (buf.data_ptr(), buf.numel(), buf.dtype, self.r, float(self.compress_ratio))
+        ratio, flags = self._plan_ratio(), self._plan_flags()
+        ident = (buf.data_ptr(), buf.numel(), buf.dtype, self.r, ratio, flags)
         hit = self._plans.get(bucket.index())
         if (hit is not None and hit[2] == ident
                 and self.iter >= self._first_compressed_iter + self.layout_check_iters):
             return hit[1]
         grads = bucket.gradients()
         shapes = [tuple(g.shape) for g in grads]
-        key = (tuple(shapes), buf.dtype, buf.device, self.r, float(self.compress_ratio))
+        key = (tuple(shapes), buf.dtype, buf.device, self.r, ratio, flags)
         if hit is not None and hit[0] == key:
             self._plans[bucket.index()] = (key, hit[1], ident)
             return hit[1]
         _check_bucket_layout(buf, grads)
-        plan = BucketPlan(shapes, self.r, self.compress_ratio, buf.dtype, buf.device)
+        # (a plan replaced here -- another ratio or other flags: the c4 hook's ramp -- is dropped:
+        # one live plan per bucket index; its native plan goes with its last reference)
+        if hit is not None and hit[1].comm_registered is not None and self._comms is not None:
+            for c in (self._comms[2], self._comms[3]):  # (callback communicators keep views by address)
+                c.unregister(hit[1].sketch)
+                c.unregister(hit[1].packed)
+        plan = BucketPlan(shapes, self.r, ratio, buf.dtype, buf.device, flags)
         self._plans[bucket.index()] = (key, plan, ident)
         return plan
+
+    def _plan_ratio(self) -> float:
+        """The compress ratio of the current call's plan."""
+        return float(self.compress_ratio)
+
+    def _plan_flags(self) -> int:
+        """The N.PLAN_* flags of the current call's plan."""
+        return 0
 
     def _note_call(self, b: int) -> None:
         """Record the observed bucket order (the bucket that followed the previous call's);
@@ -811,13 +837,18 @@ def _host_projections(state, plan, bucket, seed, dtype, dev, stream):
     ahead of time) copied to a device slot on a side stream.  Returns (ring slot, V)."""
     vslot, V = -1, plan.V_ring[0]
     pre, plan.prestaged = plan.prestaged, None
+    # the c4 hook's ramp: every tensor's V from a fresh generator seeded with the call's seed
+    # (c4 :31-39), drawn on this thread (no look-ahead, no pre-staging)
+    restarted = bool(plan.flags & N.PLAN_RESTART_DRAWS)
+    if restarted:
+        pre = None
     if pre is not None and pre[0] == seed and state.v_copy_side_stream:
         # copied during the previous call: usually complete by now, so no stream wait
         vslot, V = pre[1], plan.await_projection(pre[1], stream)
         state.prestage_hits += 1
         _ht("prestaged")
     else:
-        slot = state._proj.get(seed, plan.ms, dtype)
+        slot = (state._proj.get_restarted if restarted else state._proj.get)(seed, plan.ms, dtype)
         _ht("proj_get")
         if plan.info.v_len:  # 512 KiB pinned H2D at headline, on a side stream, ahead of encode
             cs = state._side_stream(state._copy_streams, dev, COPY_PRIORITY) if state.v_copy_side_stream else stream
@@ -827,6 +858,8 @@ def _host_projections(state, plan, bucket, seed, dtype, dev, stream):
         else:
             state._proj.release(slot)
     _ht("stage_v")
+    if restarted:
+        return vslot, V
     state._proj.prefetch(state._upcoming_ms(bucket), dtype)
     _ht("prefetch")
     if state.v_copy_side_stream:

@@ -132,6 +132,17 @@ def draw_host(seed: int, ms: Sequence[int], r: int, dtype: torch.dtype, pin: boo
     return host
 
 
+def draw_host_into(seed: int, m: int, r: int, dtype: torch.dtype, out: torch.Tensor) -> None:
+    """One tensor's [m][r] projection from a FRESH CPU generator seeded with `seed`
+    (``torch.empty(m, r).normal_(generator=g)``: the c4 hook's deterministic projections,
+    group_topk_hook_no_reshape_c4.py:31-39), into the contiguous host view `out` (m * r values)."""
+    n = int(m) * r
+    if native_ok(dtype):
+        _draw_native(seed, (ctypes.c_int64 * 1)(n), 1, dtype, out)
+    else:
+        out.view(int(m), r).normal_(generator=torch.Generator().manual_seed(int(seed)))
+
+
 class Slot:
     """A reusable pinned host buffer for one column list."""
 
@@ -260,6 +271,25 @@ class ProjectionSource:
             return slot
         self.misses += 1
         return self._slot(ms, dtype).fill(seed)
+
+    def get_restarted(self, seed: int, ms: Tuple[int, ...], dtype: torch.dtype) -> Slot:
+        """A slot whose every tensor is drawn by a fresh generator seeded with `seed` (the c4
+        hook's ramp): one draw per distinct m, on the calling thread; handed back with
+        :meth:`release` like any other."""
+        slot = self._slot(ms, dtype)
+        if slot.pending:  # the previous H2D copy from this buffer must be done
+            slot.event.synchronize()
+            slot.pending = False
+        off, drawn = 0, {}
+        for m in ms:
+            n = int(m) * self.r
+            if m in drawn:
+                slot.host[off:off + n].copy_(slot.host[drawn[m]:drawn[m] + n])
+            else:
+                draw_host_into(seed, m, self.r, dtype, slot.host[off:off + n])
+                drawn[m] = off
+            off += n
+        return slot
 
     def try_get(self, seed: int, ms: Tuple[int, ...], dtype: torch.dtype) -> Optional[Slot]:
         """The prefetched draw for (seed, ms, dtype) if it has already completed, else None

@@ -133,7 +133,9 @@ def register_comm_hook_for_ddp_model(model, process_group, args, optimizer=None)
 
     Same dispatch as the reference (utils.py:91-140): ``topk_sync``/``randk_sync`` ->
     the gradual-ratio sparse hook (sparse_hook_c4), ``group_topk_no_reshape`` -> ARC-TopK,
-    ``none`` -> dense all-reduce hook, ``noop`` -> no communication; anything else
+    ``group_topk_no_reshape_c4`` -> its c4 variant (dense 1-D tensors, gradual ratio: the hook
+    the reference's registry imports for the Llama / C4 runs, utils.py:109-110, with that
+    state's own defaults), ``none`` -> dense all-reduce hook, ``noop`` -> no communication; anything else
     raises ``ValueError``.
     """
     hook_state = None
@@ -145,9 +147,13 @@ def register_comm_hook_for_ddp_model(model, process_group, args, optimizer=None)
             random="randk" in args.compressor, start_compress_iter=args.start_compress_iter,
             random_seed=args.seed)
         model.register_comm_hook(hook_state, sparse_hook_sync)
-    elif args.compressor == "group_topk_no_reshape":
-        from allreducetopk_amd.comm_hooks.group_topk_hook_no_reshape import (GroupTopKState,
-                                                                              group_topk_hook)
+    elif args.compressor in ("group_topk_no_reshape", "group_topk_no_reshape_c4"):
+        if args.compressor.endswith("_c4"):
+            from allreducetopk_amd.comm_hooks.group_topk_hook_no_reshape_c4 import (GroupTopKState,
+                                                                                     group_topk_hook)
+        else:
+            from allreducetopk_amd.comm_hooks.group_topk_hook_no_reshape import (GroupTopKState,
+                                                                                  group_topk_hook)
         hook_state = GroupTopKState(
             process_group=process_group, r=args.r, use_error_feedback=args.use_error_feedback,
             seed=args.seed, start_compress_iter=args.start_compress_iter,

@@ -551,13 +551,15 @@ struct PackRide {
     int32_t* dfirst;
     int32_t n;  // chunks (blocks); 0: none
 };
-template <typename T, int EF>
+// DENSE false: the chunk table holds no DENSE segment's chunks (the encode kernels' riding packs:
+// their code stays as it is without that path); dense_in: the step's err_in (dense_pack)
+template <typename T, int EF, bool DENSE = true>
 __device__ __forceinline__ void pack_chunk(const SegDev* __restrict__ segs, const Chunk ch,
                                            const T* __restrict__ G, T* __restrict__ E,
                                            const int32_t* __restrict__ rowlist,
                                            const int32_t* __restrict__ slotmap,
                                            T* __restrict__ packed, int32_t* __restrict__ dfirst,
-                                           int32_t* __restrict__ rs);
+                                           int32_t* __restrict__ rs, int dense_in = 0);
 
 // One tile per block (after the riding pack's chunks).
 template <typename T, int R, int EF, bool ERR_IN>
@@ -570,8 +572,8 @@ __global__ void __launch_bounds__(256) k_encode(const SegDev* __restrict__ segs,
                                                 uint32_t* __restrict__ keys, PackRide<T> pr) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     if ((int)blockIdx.x < pr.n) {
-        pack_chunk<T, EF>(pr.segs, pr.chunks[blockIdx.x], pr.G, pr.E, pr.rowlist, pr.slotmap, pr.packed,
-                          pr.dfirst, reinterpret_cast<int32_t*>(lds));
+        pack_chunk<T, EF, false>(pr.segs, pr.chunks[blockIdx.x], pr.G, pr.E, pr.rowlist, pr.slotmap, pr.packed,
+                                 pr.dfirst, reinterpret_cast<int32_t*>(lds));
         return;
     }
     encode_tile<T, R, EF, ERR_IN>(segs, tiles[blockIdx.x - pr.n], G, E, V, sketch, part_buf, keys, lds);
@@ -589,8 +591,8 @@ __global__ void __launch_bounds__(256) k_encode_short(const SegDev* __restrict__
                                                       PackRide<T> pr) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     if ((int)blockIdx.x < pr.n) {
-        pack_chunk<T, EF>(pr.segs, pr.chunks[blockIdx.x], pr.G, pr.E, pr.rowlist, pr.slotmap, pr.packed,
-                          pr.dfirst, reinterpret_cast<int32_t*>(lds));
+        pack_chunk<T, EF, false>(pr.segs, pr.chunks[blockIdx.x], pr.G, pr.E, pr.rowlist, pr.slotmap, pr.packed,
+                                 pr.dfirst, reinterpret_cast<int32_t*>(lds));
         return;
     }
     encode_tile<T, R, EF, ERR_IN, false>(segs, tiles[blockIdx.x - pr.n], G, E, V, sketch, part_buf, keys, lds);
@@ -622,8 +624,8 @@ __global__ void __launch_bounds__(256) k_encode_carry(const SegDev* __restrict__
                                                             EncRide<T> er) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     if ((int)blockIdx.x < pr.n) {
-        pack_chunk<T, EF>(pr.segs, pr.chunks[blockIdx.x], pr.G, pr.E, pr.rowlist, pr.slotmap, pr.packed,
-                          pr.dfirst, reinterpret_cast<int32_t*>(lds));
+        pack_chunk<T, EF, false>(pr.segs, pr.chunks[blockIdx.x], pr.G, pr.E, pr.rowlist, pr.slotmap, pr.packed,
+                                 pr.dfirst, reinterpret_cast<int32_t*>(lds));
         return;
     }
     const int b = (int)blockIdx.x - pr.n;
@@ -688,6 +690,7 @@ __global__ void __launch_bounds__(256) k_energy(const SegDev* __restrict__ segs,
                                                 uint32_t* __restrict__ keys, float* __restrict__ energy) {
     const int si = blockIdx.y;
     const SegDev s = segs[si];
+    if (s.kind == ARCTOPK_SEG_DENSE) return;  // no sketch, no energies (its entries are left as they are)
     const int stride = (s.kind == ARCTOPK_SEG_RAW) ? 1 : R;
     for (int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x; row < s.n;
          row += (int64_t)gridDim.x * 256) {
@@ -1839,6 +1842,127 @@ __device__ __forceinline__ void arc_write_fused_range(const MItem it, int t, int
     }
 }
 
+// ---- DENSE segments (ARCTOPK_SEG_DENSE: the c4 hook's uncompressed 1-D tensors) ----
+// Every element is selected, slot = element: a chunk (mode kChunkDense: elements [row0, row0 +
+// nrows) of the segment, 256 threads) is streamed straight through without the row list or the
+// slot map.  The packed range starts quad-aligned (packed_off and the chunk size are multiples of
+// 4), so when the tensor's bucket offset is a multiple of 4 too both sides move as quads (16 B
+// fp32, 8 B bf16) with a scalar tail; otherwise (1-D tensors of odd sizes put the next ones at odd
+// offsets) bucket and packed range differ in alignment and the chunk moves as coalesced scalars.
+// The arithmetic is that of a selected row in pack_chunk / decode_chunk / finalize_chunk /
+// scatter_chunk, rounding included.
+// EF14: a DENSE segment has no encode tile, so the pack forms the encode's X = G + E (err_in; the
+// first call: X = G), rounded to T as the encode rounds it, and leaves E := 0.
+template <typename T, int EF>
+__device__ __forceinline__ void dense_pack(const SegDev& s, const Chunk& ch, const T* __restrict__ G,
+                                           T* __restrict__ E, T* __restrict__ packed, int err_in) {
+    const int64_t src = s.offset + ch.row0;
+    T* dst = packed + s.packed_off + ch.row0;
+    const int n = (int)ch.nrows;
+    int done = 0;
+    if ((src & 3) == 0) {
+        const int nq = n >> 2;
+        const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int q = threadIdx.x; q < nq; q += 256) {
+            float4 v;
+            if constexpr (EF == ARCTOPK_EF_NONE) {
+                v = ldq<T, kNtPack>(G + src, q);
+            } else if constexpr (EF == ARCTOPK_EF14) {
+                v = ldq<T, kNtPack>(G + src, q);
+                if (err_in) {
+                    const float4 e = ldq<T, kNtPack>(E + src, q);
+                    v = rnd4<T>(make_float4(v.x + e.x, v.y + e.y, v.z + e.z, v.w + e.w));
+                }
+                stq<T, kNtPack>(E + src, q, z4);
+            } else {
+                const float4 g = ldq<T, kNtPack>(G + src, q), e = ldq<T, kNtPack>(E + src, q);
+                v = rnd4<T>(make_float4(g.x - e.x, g.y - e.y, g.z - e.z, g.w - e.w));
+                stq<T, kNtPack>(E + src, q, make_float4(e.x + v.x, e.y + v.y, e.z + v.z, e.w + v.w));
+            }
+            stq<T, false>(dst, q, v);
+        }
+        done = nq << 2;
+    }
+    for (int i = done + (int)threadIdx.x; i < n; i += 256) {
+        float v;
+        if constexpr (EF == ARCTOPK_EF_NONE) {
+            v = ld1<T>(G + src + i);
+        } else if constexpr (EF == ARCTOPK_EF14) {
+            v = ld1<T>(G + src + i);
+            if (err_in) v = rnd<T>(v + ld1<T>(E + src + i));
+            st1<T>(E + src + i, 0.f);
+        } else {
+            const float e = ld1<T>(E + src + i);
+            v = rnd<T>(ld1<T>(G + src + i) - e);
+            st1<T>(E + src + i, e + v);
+        }
+        st1<T>(dst + i, v);
+    }
+}
+
+// out = mean of the all-reduced values (EF21: gE + mean, gE := out)
+template <typename T, int EF>
+__device__ __forceinline__ void dense_decode(const SegDev& s, const Chunk& ch, const T* __restrict__ packed,
+                                             const Scale& sc, T* __restrict__ gE, T* __restrict__ out) {
+    const int64_t base = s.offset + ch.row0;
+    const T* pk = packed + s.packed_off + ch.row0;
+    const int n = (int)ch.nrows;
+    int done = 0;
+    if ((base & 3) == 0) {
+        const int nq = n >> 2;
+        for (int q = threadIdx.x; q < nq; q += 256) {
+            float4 v = rnd4<T>(sc(ldq<T, false>(pk, q)));
+            if constexpr (EF == ARCTOPK_EF21) {
+                const float4 g = ldq<T, kNtDecode>(gE + base, q);
+                v = rnd4<T>(make_float4(g.x + v.x, g.y + v.y, g.z + v.z, g.w + v.w));
+                stq<T, kNtDecode>(gE + base, q, v);
+            }
+            stq<T, kNtDecode>(out + base, q, v);
+        }
+        done = nq << 2;
+    }
+    for (int i = done + (int)threadIdx.x; i < n; i += 256) {
+        float v = rnd<T>(sc(to_f(pk[i])));
+        if constexpr (EF == ARCTOPK_EF21) {
+            v = rnd<T>(ld1<T>(gE + base + i) + v);
+            st1<T>(gE + base + i, v);
+        }
+        st1<T>(out + base + i, v);
+    }
+}
+
+// world size 1, pack + decode fused (finalize_chunk): EF14: out := (G + E) / 1 with G the bucket
+// `out` itself (err_in; the first call: G), E := 0; noef: the bucket already holds its own (all
+// selected) values
+template <typename T>
+__device__ __forceinline__ void dense_finalize(const SegDev& s, const Chunk& ch, T* __restrict__ E,
+                                               T* __restrict__ out, int fin, const Scale& sc, int err_in) {
+    if (fin != 1) return;
+    const int64_t base = s.offset + ch.row0;
+    const int n = (int)ch.nrows;
+    int done = 0;
+    if ((base & 3) == 0) {
+        const int nq = n >> 2;
+        const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int q = threadIdx.x; q < nq; q += 256) {
+            float4 v = ldq<T, false>(out + base, q);
+            if (err_in) {
+                const float4 e = ldq<T, kNtDecode>(E + base, q);
+                v = rnd4<T>(make_float4(v.x + e.x, v.y + e.y, v.z + e.z, v.w + e.w));
+            }
+            stq<T, kNtDecode>(E + base, q, z4);
+            stq<T, kNtDecode>(out + base, q, rnd4<T>(sc(v)));
+        }
+        done = nq << 2;
+    }
+    for (int i = done + (int)threadIdx.x; i < n; i += 256) {
+        float v = ld1<T>(out + base + i);
+        if (err_in) v = rnd<T>(v + ld1<T>(E + base + i));
+        st1<T>(E + base + i, 0.f);
+        st1<T>(out + base + i, rnd<T>(sc(v)));
+    }
+}
+
 // A deferred decode (an earlier bucket's, arctopk_exchange_step's `ride`) riding in a launch of
 // the current bucket's select: its chunks run as extra 256-thread blocks after the select's own
 // (latency-bound) blocks, so the select's latency hides behind the decode's HBM stream.
@@ -1855,6 +1979,7 @@ struct DecodeRide {
     int32_t n;    // chunks (blocks); 0: none
     int32_t fin;  // world size 1, pack and decode fused (finalize_chunk): 1 EF14, 2 noef; 0: decode
     T* E;         // (fin) the residual the selected rows are taken from
+    int32_t dense_in;  // (fin 1) the step's err_in, for its DENSE segments (dense_finalize)
 };
 
 // World size 1, pack + decode in one pass (no packed buffer): the all-reduce is the identity, so
@@ -1862,15 +1987,23 @@ struct DecodeRide {
 // E on selected rows, 0 elsewhere, and the selected rows of E := 0 (what k_pack then k_decode
 // leave); noef: out is the bucket itself (G, in place), whose unselected elements become 0.  One
 // decode chunk (its row range) per 256-thread block.
-template <typename T>
+// DENSE false (here and in decode_chunk / ride_chunk): the chunk table holds no DENSE segment's
+// chunks -- the stand-alone decode kernels of plans without them, whose code stays as it is
+template <typename T, bool DENSE = true>
 __device__ __forceinline__ void finalize_chunk(const SegDev* __restrict__ segs, const Chunk ch,
                                                const int32_t* __restrict__ slotmap, T* __restrict__ E,
-                                               T* __restrict__ out, int fin, Scale sc) {
+                                               T* __restrict__ out, int fin, Scale sc, int dense_in) {
     // the decode's own arithmetic on the selected values (x / 1, rounded to T: bit-identical to
     // k_decode's output from the packed copy, NaNs included)
     auto mean4 = [&](float4 v) { return rnd4<T>(sc(v)); };
     auto mean1 = [&](float v) { return rnd<T>(sc(v)); };
     const SegDev s = segs[ch.seg];
+    if constexpr (DENSE) {
+        if (ch.mode == kChunkDense) {
+            dense_finalize<T>(s, ch, E, out, fin, sc, dense_in);
+            return;
+        }
+    }
     const int m = (int)s.m;
     const int64_t base = s.offset + ch.row0 * m;
     const int32_t* sm = slotmap + s.row_off + ch.row0;
@@ -1968,7 +2101,7 @@ __device__ __forceinline__ void finalize_chunk(const SegDev* __restrict__ segs, 
     }
     for (int64_t e = pre + 4 * nq + threadIdx.x; e < cnt; e += 256) one(e);
 }
-template <typename T, int EF>
+template <typename T, int EF, bool DENSE = true>
 __device__ __forceinline__ void decode_chunk(const SegDev* __restrict__ segs, const Chunk ch,
                                              const int32_t* __restrict__ dfc,
                                              const T* __restrict__ packed,
@@ -1986,6 +2119,10 @@ __device__ __forceinline__ void scatter_chunk(const SegDev* __restrict__ segs, c
     auto mean4 = [&](float4 v) { return rnd4<T>(sc(v)); };
     auto mean1 = [&](float v) { return rnd<T>(sc(v)); };
     const SegDev s = segs[ch.seg];
+    if (ch.mode == kChunkDense) {  // every element selected: the plain decode
+        dense_decode<T, ARCTOPK_EF_NONE>(s, ch, packed, sc, nullptr, out);
+        return;
+    }
     const int m = (int)s.m;
     const int64_t base = s.offset + ch.row0 * m;
     const int32_t* sm = slotmap + s.row_off + ch.row0;
@@ -2012,15 +2149,15 @@ __device__ __forceinline__ void scatter_chunk(const SegDev* __restrict__ segs, c
 }
 
 // chunk c of a ride: its decode, or (world size 1, fin) the fused pack + decode
-template <typename T, int EF>
+template <typename T, int EF, bool DENSE = true>
 __device__ __forceinline__ void ride_chunk(const DecodeRide<T>& d, int c, float* __restrict__ dlds) {
     if constexpr (EF != ARCTOPK_EF21) {
         if (d.fin) {
-            finalize_chunk<T>(d.segs, d.chunks[c], d.slotmap, d.E, d.out, d.fin, d.sc);
+            finalize_chunk<T, DENSE>(d.segs, d.chunks[c], d.slotmap, d.E, d.out, d.fin, d.sc, d.dense_in);
             return;
         }
     }
-    decode_chunk<T, EF>(d.segs, d.chunks[c], d.dfirst + c, d.packed, d.slotmap, d.sc, d.gE, d.out, dlds);
+    decode_chunk<T, EF, DENSE>(d.segs, d.chunks[c], d.dfirst + c, d.packed, d.slotmap, d.sc, d.gE, d.out, dlds);
 }
 
 // grid: [write ranges (nflat)] [small selects] [ride decode chunks (dr.n)] [V draw (job.n)]
@@ -2339,14 +2476,20 @@ __device__ __forceinline__ void pack_stream_small(const SegDev& s, const Chunk& 
 
 // One pack chunk (256 threads): k_pack's block, or a block of the next bucket's encode launch
 // that this bucket's pack rides in (world size 1, PackRide).  rs: LDS for kSmallTileRows rows.
-template <typename T, int EF>
+template <typename T, int EF, bool DENSE>
 __device__ __forceinline__ void pack_chunk(const SegDev* __restrict__ segs, const Chunk ch,
                                            const T* __restrict__ G, T* __restrict__ E,
                                            const int32_t* __restrict__ rowlist,
                                            const int32_t* __restrict__ slotmap,
                                            T* __restrict__ packed, int32_t* __restrict__ dfirst,
-                                           int32_t* __restrict__ rs) {
+                                           int32_t* __restrict__ rs, int dense_in) {
     const SegDev s = segs[ch.seg];
+    if constexpr (DENSE) {
+        if (ch.mode == kChunkDense) {
+            dense_pack<T, EF>(s, ch, G, E, packed, dense_in);
+            return;
+        }
+    }
     const int m = (int)s.m;
     if constexpr (sizeof(T) == 4) {
         if (ch.mode == 1) {  // m in {1, 2}: stream every row's quad of E / G with the slot map
@@ -2612,9 +2755,10 @@ __global__ void __launch_bounds__(256) k_pack(const SegDev* __restrict__ segs,
                                               const T* __restrict__ G, T* __restrict__ E,
                                               const int32_t* __restrict__ rowlist,
                                               const int32_t* __restrict__ slotmap,
-                                              T* __restrict__ packed, int32_t* __restrict__ dfirst) {
+                                              T* __restrict__ packed, int32_t* __restrict__ dfirst,
+                                              int dense_in) {
     __shared__ int32_t rs[kSmallTileRows];
-    pack_chunk<T, EF>(segs, chunks[blockIdx.x], G, E, rowlist, slotmap, packed, dfirst, rs);
+    pack_chunk<T, EF, true>(segs, chunks[blockIdx.x], G, E, rowlist, slotmap, packed, dfirst, rs, dense_in);
 }
 
 // ---------------------------------------------------------------------------
@@ -2622,7 +2766,7 @@ __global__ void __launch_bounds__(256) k_pack(const SegDev* __restrict__ segs,
 // ---------------------------------------------------------------------------
 // One decode chunk (256 threads): k_decode's block, or a block of another launch that a
 // deferred decode rides in (k_select_small_dec).  dlds: the small-m chunk tile (dynamic LDS).
-template <typename T, int EF>
+template <typename T, int EF, bool DENSE>
 __device__ __forceinline__ void decode_chunk(const SegDev* __restrict__ segs, const Chunk ch,
                                              const int32_t* __restrict__ dfc,
                                              const T* __restrict__ packed,
@@ -2633,6 +2777,12 @@ __device__ __forceinline__ void decode_chunk(const SegDev* __restrict__ segs, co
     auto mean4 = [&](float4 v) { return rnd4<T>(sc(v)); };
     auto mean1 = [&](float v) { return rnd<T>(sc(v)); };
     const SegDev s = segs[ch.seg];
+    if constexpr (DENSE) {
+        if (ch.mode == kChunkDense) {
+            dense_decode<T, EF>(s, ch, packed, sc, gE, out);
+            return;
+        }
+    }
     const int m = (int)s.m;
     const int64_t base = s.offset + ch.row0 * m;
     const int32_t* sm = slotmap + s.row_off + ch.row0;
@@ -3048,10 +3198,26 @@ __device__ __forceinline__ void decode_chunk(const SegDev* __restrict__ segs, co
     }
 }
 
+// (the stand-alone decode kernels of plans without DENSE segments: compiled without the DENSE
+// path, so they keep the code they had; plans with DENSE segments decode through k_decode2_all)
 template <typename T, int EF>
 __global__ void __launch_bounds__(256) k_decode(DecodeRide<T> d) {
     extern __shared__ __attribute__((aligned(16))) float dlds[];  // small-m chunk tile
-    ride_chunk<T, EF>(d, (int)blockIdx.x, dlds);
+    ride_chunk<T, EF, false>(d, (int)blockIdx.x, dlds);
+}
+
+// k_decode2 with the DENSE path: every stand-alone decode of plans with DENSE segments, in one
+// launch (a kernel of its own: k_decode and k_decode2 keep their code).  Two plans' whole tables
+// (the paired decode), or one plan's two chunk ranges: a plan's DENSE chunks are the last of its
+// table, so a segment range is a range of the other chunks (ride a) and one of the DENSE chunks
+// (ride b), either of which may be empty.  (Compiled as a one-ride kernel the same code reserved
+// 36 B of scratch per lane in its fp32 noef / EF14 form; this one uses none.)
+template <typename T, int EF>
+__global__ void __launch_bounds__(256) k_decode2_all(DecodeRide<T> a, DecodeRide<T> b) {
+    extern __shared__ __attribute__((aligned(16))) float dlds[];
+    const int i = (int)blockIdx.x;
+    const DecodeRide<T>& d = i < a.n ? a : b;
+    ride_chunk<T, EF, true>(d, i < a.n ? i : i - a.n, dlds);
 }
 
 // the decode into a bucket that is already zero (fin 3, the zero-ahead drain: only ever the
@@ -3070,7 +3236,7 @@ __global__ void __launch_bounds__(256) k_decode2(DecodeRide<T> a, DecodeRide<T> 
     const int i = (int)blockIdx.x;
     const DecodeRide<T>& d = i < a.n ? a : b;
     const int c = i < a.n ? i : i - a.n;
-    ride_chunk<T, EF>(d, c, dlds);
+    ride_chunk<T, EF, false>(d, c, dlds);
 }
 
 // A deferred decode (an earlier bucket's, arctopk_exchange_step's `ride`) riding in the
@@ -3232,7 +3398,7 @@ int launch_encode_r(const arctopk_plan* p, const T* G, T* E, int ef, int err_in,
     }
     if (p->n_split == 0) {
         // (no encode launch at all: nothing for `done` to follow but the stream itself)
-        if (done && !(p->n_enc > 0 || pr.n > 0)) return (int)hipEventRecord(done, st);
+        if (done && !(p->n_enc > 0 || pr.n > 0 || er.n > 0)) return (int)hipEventRecord(done, st);
         return 0;
     }
     const int gx = (int)std::min<int64_t>(256, (p->split_rows_max * R + 255) / 256);
@@ -3249,6 +3415,9 @@ int launch_encode(const arctopk_plan* p, const void* grad, void* err, int ef, in
     T* E = static_cast<T*>(err);
     const T* Vt = static_cast<const T*>(V);
     T* sk = static_cast<T*>(sketch);
+    // DENSE segments have no encode tile: the step's pack (or fused pack + decode) forms EF14's
+    // X = G + E itself, with this call's err_in (host bookkeeping of the plan, like x_*)
+    const_cast<arctopk_plan*>(p)->dense_err_in = err_in;
     switch (p->r) {
         case 1: return launch_encode_r<T, 1>(p, G, E, ef, err_in, Vt, sk, keys, st, pr, done, er, er_lds, er_short);
         case 2: return launch_encode_r<T, 2>(p, G, E, ef, err_in, Vt, sk, keys, st, pr, done, er, er_lds, er_short);
@@ -3273,6 +3442,8 @@ EncRide<T> make_enc_ride(const arctopk_plan* p, int ef, int err_in, int* lds) {
     er.segs = c->d_segs;
     er.tiles = use_e ? c->d_enc_e : c->d_enc;
     er.n = use_e ? c->n_enc_e : c->n_enc;
+    // (its DENSE segments' EF14 pre-apply is formed by its pack / fused decode: see launch_encode)
+    const_cast<arctopk_plan*>(c)->dense_err_in = err_in;
     er.G = static_cast<const T*>(c->x_t_bucket);
     er.E = static_cast<T*>(c->x_t_err);
     er.V = static_cast<const T*>(c->x_t_V ? c->x_t_V : c->b_V);
@@ -3333,6 +3504,7 @@ DecodeRide<T> make_ride(const RideArgs* ra) {
     dr.fin = ride_fin(rp, ra->ef);
     if (dr.fin == 3) dr.fin = 0;  // (a ride never follows a zero-ahead; a whole decode is right anyway)
     dr.E = static_cast<T*>(rp->x_err);
+    dr.dense_in = rp->dense_err_in;
     return dr;
 }
 
@@ -3520,13 +3692,13 @@ int launch_select(const arctopk_plan* p, const void* sketch_, int32_t ws, int32_
 template <typename T, int EF>
 void pack_launch(dim3 grid, hipStream_t st, hipEvent_t done, const SegDev* segs, const Chunk* ch,
                  const T* grad, T* err, const int32_t* rowlist, const int32_t* slotmap, T* packed,
-                 int32_t* dfirst) {
+                 int32_t* dfirst, int dense_in) {
     if (done)
         hipExtLaunchKernelGGL((k_pack<T, EF>), grid, dim3(256), 0, st, nullptr, done, 0, segs, ch, grad, err,
-                              rowlist, slotmap, packed, dfirst);
+                              rowlist, slotmap, packed, dfirst, dense_in);
     else
         hipLaunchKernelGGL((k_pack<T, EF>), grid, dim3(256), 0, st, segs, ch, grad, err, rowlist, slotmap,
-                           packed, dfirst);
+                           packed, dfirst, dense_in);
 }
 
 template <typename T>
@@ -3539,11 +3711,14 @@ int launch_pack(const arctopk_plan* p, int c0, int c1, const void* grad_, void* 
     dim3 grid(c1 - c0);
     const Chunk* ch = p->d_pack + c0;
     if (ef == ARCTOPK_EF_NONE)
-        pack_launch<T, ARCTOPK_EF_NONE>(grid, st, done, p->d_segs, ch, grad, err, rowlist, slotmap, packed, p->d_dfirst);
+        pack_launch<T, ARCTOPK_EF_NONE>(grid, st, done, p->d_segs, ch, grad, err, rowlist, slotmap, packed, p->d_dfirst,
+                                     p->dense_err_in);
     else if (ef == ARCTOPK_EF14)
-        pack_launch<T, ARCTOPK_EF14>(grid, st, done, p->d_segs, ch, grad, err, rowlist, slotmap, packed, p->d_dfirst);
+        pack_launch<T, ARCTOPK_EF14>(grid, st, done, p->d_segs, ch, grad, err, rowlist, slotmap, packed, p->d_dfirst,
+                                     p->dense_err_in);
     else if (ef == ARCTOPK_EF21)
-        pack_launch<T, ARCTOPK_EF21>(grid, st, done, p->d_segs, ch, grad, err, rowlist, slotmap, packed, p->d_dfirst);
+        pack_launch<T, ARCTOPK_EF21>(grid, st, done, p->d_segs, ch, grad, err, rowlist, slotmap, packed, p->d_dfirst,
+                                     p->dense_err_in);
     else
         return ARCTOPK_EINVAL;
     return (int)hipGetLastError();
@@ -3588,20 +3763,33 @@ __global__ void __launch_bounds__(256) k_dfirst(const SegDev* __restrict__ segs,
     }
 }
 
-// `done` as in pack_launch (the decode after an inline all-reduce, watched by exchange.cpp)
-template <typename T, int EF>
-void decode_launch(dim3 grid, size_t lds, hipStream_t st, hipEvent_t done, const DecodeRide<T>& d) {
-    if (done)
-        hipExtLaunchKernelGGL((k_decode<T, EF>), grid, dim3(256), lds, st, nullptr, done, 0, d);
-    else
-        hipLaunchKernelGGL((k_decode<T, EF>), grid, dim3(256), lds, st, d);
+// DENSE segments (one block each): rowlist[sel_off + i] = i, slotmap[row_off + i] = i
+__global__ void __launch_bounds__(256) k_dense_identity(const SegDev* __restrict__ segs,
+                                                        const int32_t* __restrict__ ids,
+                                                        int32_t* __restrict__ rowlist,
+                                                        int32_t* __restrict__ slotmap) {
+    const SegDev s = segs[ids[blockIdx.x]];
+    for (int64_t i = threadIdx.x; i < s.n; i += 256) {
+        rowlist[s.sel_off + i] = (int32_t)i;
+        slotmap[s.row_off + i] = (int32_t)i;
+    }
 }
 
-// decode chunks [c0, c1) of plan p; fin (world size 1): the fused pack + decode from residual E
+// `done` as in pack_launch (the decode after an inline all-reduce, watched by exchange.cpp)
+template <typename... KArgs, typename T>
+void decode_launch(void (*k)(KArgs...), int n, size_t lds, hipStream_t st, hipEvent_t done, const DecodeRide<T>& d) {
+    if (done) hipExtLaunchKernelGGL(k, dim3(n), dim3(256), lds, st, nullptr, done, 0, d);
+    else hipLaunchKernelGGL(k, dim3(n), dim3(256), lds, st, d);
+}
+
+// decode chunks [c0, c1) of plan p (none of a DENSE segment) and its DENSE chunks [d0, d1);
+// fin (world size 1): the fused pack + decode from residual E.  `done` is completed by the last
+// launch (one of the ranges is not empty).
 template <typename T>
 int launch_decode(const arctopk_plan* p, int c0, int c1, const int32_t* dfirst, const void* packed_,
                   const int32_t* slotmap, int32_t ws, int32_t ef, void* gerr_, void* out_, hipStream_t st,
-                  hipEvent_t done = nullptr, int fin = 0, void* E = nullptr) {
+                  hipEvent_t done = nullptr, int fin = 0, void* E = nullptr, int d0 = 0, int d1 = 0) {
+    if (ef != ARCTOPK_EF21 && ef != ARCTOPK_EF_NONE && ef != ARCTOPK_EF14) return ARCTOPK_EINVAL;
     DecodeRide<T> d{};
     d.segs = p->d_segs;
     d.chunks = p->d_dec + c0;
@@ -3614,17 +3802,29 @@ int launch_decode(const arctopk_plan* p, int c0, int c1, const int32_t* dfirst, 
     d.n = c1 - c0;
     d.fin = fin;
     d.E = static_cast<T*>(E);
-    const dim3 grid(c1 - c0);
+    d.dense_in = p->dense_err_in;
+    DecodeRide<T> dd = d;
+    dd.chunks = p->d_dec + d0;
+    dd.dfirst = dfirst + d0;
+    dd.n = d1 - d0;
     const size_t lds = (size_t)p->dec_lds_bytes;
-    if (fin == 3) {
-        if (done) hipExtLaunchKernelGGL(k_decode_scatter<T>, grid, dim3(256), 0, st, nullptr, done, 0, d);
-        else hipLaunchKernelGGL(k_decode_scatter<T>, grid, dim3(256), 0, st, d);
-    } else if (ef == ARCTOPK_EF21 && !fin)
-        decode_launch<T, ARCTOPK_EF21>(grid, lds, st, done, d);
-    else if (ef == ARCTOPK_EF_NONE || ef == ARCTOPK_EF14)
-        decode_launch<T, ARCTOPK_EF_NONE>(grid, lds, st, done, d);
-    else
-        return ARCTOPK_EINVAL;
+    const bool ef21 = ef == ARCTOPK_EF21 && !fin;
+    if (fin == 3) {  // the zero-ahead scatter handles both kinds of chunk: one launch per range
+        if (d.n > 0 && dd.n > 0 && c1 == d0) {  // (a whole plan: the ranges are one)
+            d.n += dd.n;
+            dd.n = 0;
+        }
+        if (d.n > 0) decode_launch(&k_decode_scatter<T>, d.n, 0, st, dd.n > 0 ? nullptr : done, d);
+        if (dd.n > 0) decode_launch(&k_decode_scatter<T>, dd.n, 0, st, done, dd);
+    } else if (dd.n > 0) {  // a plan with DENSE segments: both ranges in one launch
+        const dim3 grid(d.n + dd.n);
+        if (ef21) launch_done(&k_decode2_all<T, ARCTOPK_EF21>, grid, dim3(256), lds, st, done, d, dd);
+        else launch_done(&k_decode2_all<T, ARCTOPK_EF_NONE>, grid, dim3(256), lds, st, done, d, dd);
+    } else if (ef21) {
+        decode_launch(&k_decode<T, ARCTOPK_EF21>, d.n, lds, st, done, d);
+    } else {
+        decode_launch(&k_decode<T, ARCTOPK_EF_NONE>, d.n, lds, st, done, d);
+    }
     return (int)hipGetLastError();
 }
 
@@ -3640,6 +3840,21 @@ extern "C" int arctopk_encode(const arctopk_plan* p, const void* grad, void* err
     if (p->dtype == ARCTOPK_BF16) return launch_encode<bf16_t>(p, grad, err, ef, err_in, V, sketch, nullptr, st);
     return launch_encode<float>(p, grad, err, ef, err_in, V, sketch, nullptr, st);
 }
+
+namespace arctopk {
+int dense_tables(const arctopk_plan* p, int32_t* rowlist, int32_t* slotmap, void* stream) {
+    if (!p || p->n_dense == 0) return 0;
+    if (!rowlist || !slotmap) return ARCTOPK_EINVAL;
+    const bool bound = rowlist == p->b_rowlist && slotmap == p->b_slotmap;
+    if (bound && p->dense_init) return 0;
+    hipLaunchKernelGGL(k_dense_identity, dim3(p->n_dense), dim3(256), 0, (hipStream_t)stream,
+                       (const SegDev*)p->d_segs, (const int32_t*)p->d_dense, rowlist, slotmap);
+    const hipError_t e = hipGetLastError();
+    // (host bookkeeping of the plan, like the exchange step's x_* fields)
+    if (e == hipSuccess && bound) const_cast<arctopk_plan*>(p)->dense_init = 1;
+    return (int)e;
+}
+}  // namespace arctopk
 
 namespace arctopk {
 // arctopk_encode at world size 1 for this plan's own select (keys mode): multi-block select
@@ -3658,7 +3873,8 @@ int encode_keyed(const arctopk_plan* p, const void* grad, void* err, int32_t ef,
     uint32_t* keys = p->any_keyed ? p->d_keys : nullptr;
     // the ride: rp's pack (its bound row list, slot map and packed buffer; its bucket and residual)
     // as the launch's first blocks -- same dtype, and buffers distinct from this call's
-    const bool take = rp && rode && rp->dtype == p->dtype && rp->device == p->device && rp->n_pack > 0 &&
+    // (not a plan with DENSE segments: the encode kernels' riding packs are compiled without them)
+    const bool take = rp && rode && rp->n_dense == 0 && rp->dtype == p->dtype && rp->device == p->device && rp->n_pack > 0 &&
                       rp->b_rowlist && rp->b_slotmap && rp->b_packed && (ef == ARCTOPK_EF14 ? rp_err : rp_grad) &&
                       (ef != ARCTOPK_EF21 || rp_err) && rp_grad != grad && (!rp_err || rp_err != err);
     if (p->dtype == ARCTOPK_BF16) {
@@ -3713,6 +3929,7 @@ int arctopk::select_draw_keyed(const arctopk_plan* p, const void* sketch, int32_
     if (!p || !sketch || !rowlist || !slotmap || ws < 1 || (keyed && ws != 1)) return ARCTOPK_EINVAL;
     if (next && (!next_V || next->dtype != p->dtype || next->device != p->device)) return ARCTOPK_EINVAL;
     hipStream_t st = (hipStream_t)stream;
+    if (int de = dense_tables(p, rowlist, slotmap, stream)) return de;
     VDrawJob job{};
     if (next && next->n_vchunk) {
         job.segs = next->d_vdraw;
@@ -3748,6 +3965,7 @@ int launch_select_ride(const arctopk_plan* p, const void* sketch_, int32_t ws, i
     dr.fin = ride_fin(rp, rp_ef);
     if (dr.fin == 3) dr.fin = 0;
     dr.E = static_cast<T*>(rp->x_err);
+    dr.dense_in = rp->dense_err_in;
     const size_t shm = (size_t)std::max(p->small_lds, rp->dec_lds_bytes);
     const dim3 grid(p->n_small + dr.n + job.n);
     const T* sketch = static_cast<const T*>(sketch_);
@@ -3786,6 +4004,7 @@ int select_ride(const arctopk_plan* p, const void* sketch, int32_t ws, int32_t* 
                 int32_t rp_ws, int32_t rp_ef, void* rp_gerr, void* rp_out, int* rode, void* stream, bool keyed) {
     *rode = 0;
     if (keyed && ws != 1) return ARCTOPK_EINVAL;
+    if (int de = dense_tables(p, rowlist, slotmap, stream)) return de;
     constexpr int64_t big_rows = ARCTOPK_SEL_BIG_ROWS;
     const bool rideable = rp && rp->dtype == p->dtype && rp->device == p->device && rp->n_dec > 0 &&
                           rp->b_packed && rp->b_slotmap && rp_out && (rp_ef != ARCTOPK_EF21 || rp_gerr) &&
@@ -3850,6 +4069,7 @@ extern "C" int arctopk_pack_segments(const arctopk_plan* p, int32_t seg_begin, i
     if (ef < 0 || ef > 2) return ARCTOPK_EINVAL;
     if (ef == ARCTOPK_EF_NONE ? !grad : !err) return ARCTOPK_EINVAL;
     if (ef == ARCTOPK_EF21 && !grad) return ARCTOPK_EINVAL;
+    if (ef == ARCTOPK_EF14 && p->n_dense && !grad) return ARCTOPK_EINVAL;  // DENSE: packed = G + E
     const int c0 = p->h_pack_begin[seg_begin], c1 = p->h_pack_begin[seg_end];
     if (c1 == c0) return 0;
     hipStream_t st = (hipStream_t)stream;
@@ -3871,6 +4091,7 @@ int pack_signal(const arctopk_plan* p, const void* grad, void* err, int32_t ef, 
     if (ef < 0 || ef > 2) return ARCTOPK_EINVAL;
     if (ef == ARCTOPK_EF_NONE ? !grad : !err) return ARCTOPK_EINVAL;
     if (ef == ARCTOPK_EF21 && !grad) return ARCTOPK_EINVAL;
+    if (ef == ARCTOPK_EF14 && p->n_dense && !grad) return ARCTOPK_EINVAL;
     const int c0 = p->h_pack_begin[0], c1 = p->h_pack_begin[p->nseg];
     if (c1 == c0) return (int)hipEventRecord((hipEvent_t)done, (hipStream_t)stream);
     hipStream_t st = (hipStream_t)stream;
@@ -3888,7 +4109,8 @@ extern "C" int arctopk_decode_segments(const arctopk_plan* p, int32_t seg_begin,
     if (ef < 0 || ef > 2) return ARCTOPK_EINVAL;
     if (ef == ARCTOPK_EF21 && !gerr) return ARCTOPK_EINVAL;
     const int c0 = p->h_dec_begin[seg_begin], c1 = p->h_dec_begin[seg_end];
-    if (c1 == c0) return 0;
+    const int d0 = p->h_ddec_begin[seg_begin], d1 = p->h_ddec_begin[seg_end];  // DENSE segments' chunks
+    if (c1 == c0 && d1 == d0) return 0;
     hipStream_t st = (hipStream_t)stream;
     // mode-3 chunks read their packed range from a chunk table; the one the plan's pack writes
     // describes the pack's own row list, so here it is derived from the slot map given (the
@@ -3899,8 +4121,10 @@ extern "C" int arctopk_decode_segments(const arctopk_plan* p, int32_t seg_begin,
         if (he != hipSuccess) return (int)he;
     }
     if (p->dtype == ARCTOPK_BF16)
-        return launch_decode<bf16_t>(p, c0, c1, p->d_dfirst_pub, packed, slotmap, ws, ef, gerr, out, st);
-    return launch_decode<float>(p, c0, c1, p->d_dfirst_pub, packed, slotmap, ws, ef, gerr, out, st);
+        return launch_decode<bf16_t>(p, c0, c1, p->d_dfirst_pub, packed, slotmap, ws, ef, gerr, out, st, nullptr, 0,
+                                     nullptr, d0, d1);
+    return launch_decode<float>(p, c0, c1, p->d_dfirst_pub, packed, slotmap, ws, ef, gerr, out, st, nullptr, 0,
+                                nullptr, d0, d1);
 }
 
 extern "C" int arctopk_decode(const arctopk_plan* p, const void* packed, const int32_t* slotmap,
@@ -3915,7 +4139,15 @@ int launch_decode_pair(const RideArgs& a, const RideArgs& b, hipStream_t st, hip
     const DecodeRide<T> da = make_ride<T>(&a), db = make_ride<T>(&b);
     const size_t lds = (size_t)std::max(a.rp->dec_lds_bytes, b.rp->dec_lds_bytes);
     const dim3 grid(da.n + db.n);
-    if (a.ef == ARCTOPK_EF21) {
+    if (a.rp->n_dense > 0 || b.rp->n_dense > 0) {  // (whole tables, DENSE chunks included)
+        if (a.ef == ARCTOPK_EF21) {
+            if (done) hipExtLaunchKernelGGL((k_decode2_all<T, ARCTOPK_EF21>), grid, dim3(256), lds, st, nullptr, done, 0, da, db);
+            else hipLaunchKernelGGL((k_decode2_all<T, ARCTOPK_EF21>), grid, dim3(256), lds, st, da, db);
+        } else {
+            if (done) hipExtLaunchKernelGGL((k_decode2_all<T, ARCTOPK_EF_NONE>), grid, dim3(256), lds, st, nullptr, done, 0, da, db);
+            else hipLaunchKernelGGL((k_decode2_all<T, ARCTOPK_EF_NONE>), grid, dim3(256), lds, st, da, db);
+        }
+    } else if (a.ef == ARCTOPK_EF21) {
         if (done) hipExtLaunchKernelGGL((k_decode2<T, ARCTOPK_EF21>), grid, dim3(256), lds, st, nullptr, done, 0, da, db);
         else hipLaunchKernelGGL((k_decode2<T, ARCTOPK_EF21>), grid, dim3(256), lds, st, da, db);
     } else {
@@ -3955,14 +4187,15 @@ int decode_signal(const arctopk_plan* p, const void* packed, const int32_t* slot
     if (ef < 0 || ef > 2) return ARCTOPK_EINVAL;
     if (ef == ARCTOPK_EF21 && !gerr) return ARCTOPK_EINVAL;
     const int c0 = p->h_dec_begin[0], c1 = p->h_dec_begin[p->nseg];
+    const int d0 = p->h_ddec_begin[0], d1 = p->h_ddec_begin[p->nseg];
     hipStream_t st = (hipStream_t)stream;
-    if (c1 == c0) return done ? (int)hipEventRecord((hipEvent_t)done, st) : 0;
+    if (c1 == c0 && d1 == d0) return done ? (int)hipEventRecord((hipEvent_t)done, st) : 0;
     const int fin = ride_fin(p, ef);
     if (p->dtype == ARCTOPK_BF16)
         return launch_decode<bf16_t>(p, c0, c1, p->d_dfirst, packed, slotmap, ws, ef, gerr, out, st, (hipEvent_t)done,
-                                     fin, p->x_err);
+                                     fin, p->x_err, d0, d1);
     return launch_decode<float>(p, c0, c1, p->d_dfirst, packed, slotmap, ws, ef, gerr, out, st, (hipEvent_t)done,
-                                fin, p->x_err);
+                                fin, p->x_err, d0, d1);
 }
 }  // namespace arctopk
 

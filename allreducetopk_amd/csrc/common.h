@@ -305,6 +305,8 @@ constexpr int kSmallTileRows = 1024;  // rows of a small-m pack/decode chunk (LD
 
 // encode tile modes
 enum : int32_t { ENC_ROW_VEC = 0, ENC_ROW_SCALAR = 1, ENC_TILE = 2, ENC_RAW = 3 };
+// pack / decode chunk mode of a DENSE segment (every element selected, no row list or slot map)
+constexpr int32_t kChunkDense = 4;
 
 struct EncTile {
     int32_t seg;
@@ -324,8 +326,9 @@ struct VDraw {         // one SKETCH tensor's torch.randn(m, r, device=...) draw
     uint64_t stride;   // threads of torch's grid-stride launch: 256 * grid
     uint64_t offset;   // Philox offset at this draw (after the bucket's manual_seed)
 };
+// restart (ARCTOPK_PLAN_RESTART_DRAWS): every draw at Philox offset 0, advance 0
 int vdraw_table(const arctopk_segment* segs, int nseg, int r, int device, VDraw* out, int* nout,
-                uint64_t* advance);
+                uint64_t* advance, bool restart = false);
 constexpr int kVChunk = 1024;  // elements of V per draw block
 struct VChunk {        // one draw block's element range [lo, hi) of draw `entry`
     int32_t entry;
@@ -346,6 +349,7 @@ struct Chunk {         // pack: selected-row range (mode 0) or row range (mode 1
                        // decode 3: 4 <= m < 256, quad-aligned chunks: the chunk's slot map and
                        //   packed rows staged in LDS, the packed range read from the chunk
                        //   table the pack wrote (d_dfirst), one round trip for the data
+                       // 4 (kChunkDense): a DENSE segment's element range, streamed straight through
     int64_t row0;
     int64_t nrows;
 };
@@ -359,6 +363,7 @@ struct arctopk_plan {
     int dtype;                    // ARCTOPK_F32 / ARCTOPK_BF16 (bucket element type)
     int r;
     double ratio;
+    int flags;                    // ARCTOPK_PLAN_*
     int nseg;
     arctopk_plan_info info;
     arctopk_segment* h_segs;      // host copy
@@ -369,6 +374,12 @@ struct arctopk_plan {
     int n_enc_e;
     int enc_lds_bytes;            // dynamic LDS of the encode launch
     int enc_short;                // no wave-per-row tile in the tables: k_encode_short
+    int dense_err_in;             // err_in of the plan's last encode: a DENSE segment has no encode
+                                  // tile, so EF14's X = G + E (err_in) or G is formed by its pack
+                                  // (or the fused pack + decode) from the bucket and the residual
+    int32_t* d_dense;             // ids of the DENSE segments, and their number
+    int n_dense;
+    int dense_init;               // the identity is in the bound row list / slot map's DENSE ranges
     float* d_part;                // partial sketches of column-split segments
     int32_t* d_split;             // ids of column-split segments
     int n_split;
@@ -378,7 +389,9 @@ struct arctopk_plan {
     arctopk::Chunk* d_dec;
     int n_dec;
     int32_t* h_pack_begin;        // [nseg + 1]: first pack chunk of each segment
-    int32_t* h_dec_begin;         // [nseg + 1]: first decode chunk of each segment
+    int32_t* h_dec_begin;         // [nseg + 1]: first decode chunk of each segment (DENSE: none here)
+    int32_t* h_ddec_begin;        // [nseg + 1]: first DENSE decode chunk of each segment: the table's
+                                  // last chunks, [h_dec_begin[nseg], n_dec)
     int dec_lds_bytes;            // dynamic LDS of the decode launch (small-m chunk tiles)
     int32_t* d_dfirst;            // [n_dec + 1]: per decode chunk, the bucket-wide index (sel_off +
                                   // slot) of its first selected row; written by the pack from the
@@ -465,6 +478,10 @@ int pack_signal(const arctopk_plan* p, const void* grad, void* err, int32_t ef, 
 // the decode of the plan's own last pack (its chunk table); `done` (may be null) completed by the kernel
 int decode_signal(const arctopk_plan* p, const void* packed, const int32_t* slotmap, int32_t ws, int32_t ef,
                   void* gerr, void* out, void* stream, void* done);
+// DENSE segments: the identity into their ranges of a row list and slot map (what a select of
+// all rows would leave).  Nothing of the library writes those ranges otherwise, so the plan's bound
+// buffers get it once per binding (the first select after arctopk_plan_bind); other buffers always.
+int dense_tables(const arctopk_plan* p, int32_t* rowlist, int32_t* slotmap, void* stream);
 // the watchdog stops looking at a plan's events (arctopk_plan_destroy)
 void exchange_forget(arctopk_plan* p);
 // the emulated wire communicator (wire.hip): one all-reduce's local cost on an R-rank ring

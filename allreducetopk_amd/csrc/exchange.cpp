@@ -632,6 +632,8 @@ extern "C" int arctopk_exchange_trail(arctopk_plan* p, void* bucket, void* err, 
     if (draw && p->info.v_len > 0) {
         if (int e = arctopk_draw_projections(p, seed, const_cast<void*>(V), stream)) return e;
     }
+    // (a carried trailing step's selects run in the carrier's launch: its DENSE ranges now)
+    if (int e = arctopk::dense_tables(p, p->b_rowlist, p->b_slotmap, stream)) return e;
     p->x_trail = 1;
     p->x_t_bucket = bucket;
     p->x_t_err = err;
@@ -761,7 +763,9 @@ extern "C" int arctopk_exchange_step(arctopk_plan* p, void* bucket, void* err, v
     if (!e) e = mark(marks, ARCTOPK_MARK_ENCODE, st);
     ht.lap(1);
     // one all-reduce for every tensor's sketch (the reference: one per tensor, :33, :58, :88)
-    if (!e && sketch_comm) e = arctopk_comm_allreduce(sketch_comm, p->b_sketch, p->info.sketch_len, p->dtype, stream);
+    // (a bucket or group of DENSE segments only has no sketch: no all-reduce)
+    if (!e && sketch_comm && p->info.sketch_len > 0)
+        e = arctopk_comm_allreduce(sketch_comm, p->b_sketch, p->info.sketch_len, p->dtype, stream);
     if (!e) e = mark(marks, ARCTOPK_MARK_SKETCH_AR, st);
     if (e) return e;
     // The select stream takes over after the encode and the sketch all-reduce: the latency-bound

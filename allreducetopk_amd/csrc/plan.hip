@@ -17,7 +17,7 @@ using namespace arctopk;
 namespace {
 
 int build_segments(const int64_t* dims, const int32_t* ndims, int32_t ntensors, int r, double ratio,
-                   std::vector<arctopk_segment>& segs, arctopk_plan_info& info) {
+                   int flags, std::vector<arctopk_segment>& segs, arctopk_plan_info& info) {
     int64_t off = 0, sk = 0, vo = 0, po = 0, ro = 0, so = 0, vals = 0;
     const int64_t* d = dims;
     for (int i = 0; i < ntensors; ++i) {
@@ -28,8 +28,8 @@ int build_segments(const int64_t* dims, const int32_t* ndims, int32_t ntensors, 
         arctopk_segment s;
         std::memset(&s, 0, sizeof(s));
         s.offset = off;
-        if (nd == 1) {                      // ref :19-41
-            s.kind = ARCTOPK_SEG_RAW;
+        if (nd == 1) {                      // ref :19-41; c4 :19-25: passed through dense
+            s.kind = (flags & ARCTOPK_PLAN_DENSE_1D) ? ARCTOPK_SEG_DENSE : ARCTOPK_SEG_RAW;
             s.n = numel;
             s.m = 1;
         } else if (nd == 2) {               // ref :44-47
@@ -50,11 +50,12 @@ int build_segments(const int64_t* dims, const int32_t* ndims, int32_t ntensors, 
         // k = max(1, int(n * ratio)): float64 product, truncation (ref cal_k :173-187)
         int64_t k = (int64_t)((double)s.n * ratio);
         if (k < 1) k = 1;
+        if (s.kind == ARCTOPK_SEG_DENSE) k = s.n;  // every element (c4 cal_k :206-207)
         if (k > s.n) return ARCTOPK_EINVAL;  // torch.topk raises for k > n
         s.k_rows = k;
         s.sketch_off = sk;
-        sk += (s.kind == ARCTOPK_SEG_RAW) ? s.n : s.n * r;
-        s.v_off = (s.kind == ARCTOPK_SEG_RAW) ? -1 : vo;
+        if (s.kind != ARCTOPK_SEG_DENSE) sk += (s.kind == ARCTOPK_SEG_RAW) ? s.n : s.n * r;
+        s.v_off = (s.kind == ARCTOPK_SEG_SKETCH) ? vo : -1;
         if (s.kind == ARCTOPK_SEG_SKETCH) vo += s.m * r;
         s.packed_off = po;
         po += k * s.m;
@@ -85,7 +86,14 @@ int build_segments(const int64_t* dims, const int32_t* ndims, int32_t ntensors, 
 extern "C" int arctopk_plan_create(const int64_t* dims, const int32_t* ndims, int32_t ntensors,
                                    int32_t r, double compress_ratio, int32_t dtype, int32_t device,
                                    arctopk_plan** out) {
+    return arctopk_plan_create_ex(dims, ndims, ntensors, r, compress_ratio, dtype, device, 0, out);
+}
+
+extern "C" int arctopk_plan_create_ex(const int64_t* dims, const int32_t* ndims, int32_t ntensors,
+                                      int32_t r, double compress_ratio, int32_t dtype, int32_t device,
+                                      int32_t flags, arctopk_plan** out) {
     if (!dims || !ndims || !out || ntensors < 1) return ARCTOPK_EINVAL;
+    if (flags & ~(ARCTOPK_PLAN_DENSE_1D | ARCTOPK_PLAN_RESTART_DRAWS)) return ARCTOPK_EINVAL;
     if (r < 1 || r > kMaxR) return ARCTOPK_EINVAL;
     if (!(compress_ratio > 0.0) || compress_ratio > 1.0) return ARCTOPK_EINVAL;
     if (dtype != ARCTOPK_F32 && dtype != ARCTOPK_BF16) return ARCTOPK_EDTYPE;
@@ -94,22 +102,23 @@ extern "C" int arctopk_plan_create(const int64_t* dims, const int32_t* ndims, in
     std::vector<arctopk_segment> segs;
     arctopk_plan_info info;
     std::memset(&info, 0, sizeof(info));
-    int st = build_segments(dims, ndims, ntensors, r, compress_ratio, segs, info);
+    int st = build_segments(dims, ndims, ntensors, r, compress_ratio, flags, segs, info);
     if (st) return st;
 
     std::vector<SegDev> dsegs(segs.size());
-    std::vector<int32_t> small_ids, large_ids, split_ids;
+    std::vector<int32_t> small_ids, large_ids, split_ids, dense_ids;
     // Single-block selects up to kSmallSelRows rows -- but in a bucket that has multi-block
     // items anyway, only the ones that fit 256-thread blocks: the rest join the multi-block
     // batch, so the batch's write launch can host the small selects (and a deferred decode)
     // and the separate refine launch is not needed
     bool any_large = false;
-    for (const arctopk_segment& s : segs) any_large = any_large || s.n > kSmallSelRows;
+    for (const arctopk_segment& s : segs)
+        any_large = any_large || (s.kind != ARCTOPK_SEG_DENSE && s.n > kSmallSelRows);
     const int64_t small_cap = any_large ? (int64_t)ARCTOPK_SMALL_SEL_ROWS_MIXED : (int64_t)kSmallSelRows;
     int64_t small_rows = 0;
     std::vector<EncTile> enc;
-    std::vector<Chunk> pack, dec;
-    std::vector<int32_t> pack_begin, dec_begin;
+    std::vector<Chunk> pack, dec, dec_dense;  // (DENSE segments' decode chunks: the table's last)
+    std::vector<int32_t> pack_begin, dec_begin, ddec_begin;
     int lds = 0;
     int64_t dec_lds = 0;
     // Encode work sizing: tiles of wave-per-row segments hold enough rows that the
@@ -117,7 +126,7 @@ extern "C" int arctopk_plan_create(const int64_t* dims, const int32_t* ndims, in
     // of a 46 MB MLP weight must still fill 256 CUs), within [8K, 64K] elements per block.
     int64_t row_work = 0;
     for (const arctopk_segment& s : segs)
-        if (s.kind != ARCTOPK_SEG_RAW && !(s.m < kSmallM && (kTileRows * s.m + s.m * r) * 4 <= 65536))
+        if (s.kind == ARCTOPK_SEG_SKETCH && !(s.m < kSmallM && (kTileRows * s.m + s.m * r) * 4 <= 65536))
             row_work += s.n * s.m;
     const int64_t target = kEncTargetBlocks;
     // (small buckets: tiles down to ARCTOPK_ENC_MIN_TILE elements -- at least one row per wave --
@@ -153,6 +162,25 @@ extern "C" int arctopk_plan_create(const int64_t* dims, const int32_t* ndims, in
         g.magic32 = s.m > 1 ? (uint32_t)(((1ull << 32) + (uint64_t)s.m - 1) / (uint64_t)s.m) : 0u;
         g.nparts = 1;
         g.part_off = 0;
+        ddec_begin.push_back((int32_t)dec_dense.size());
+        if (s.kind == ARCTOPK_SEG_DENSE) {
+            // no sketch, no select item, no encode tile (EF14's E := G + E is formed by the pack):
+            // pack / decode chunks that stream the element range straight through (chunks of a
+            // multiple of 8 elements: every chunk of the segment has the segment's alignment)
+            dense_ids.push_back((int32_t)i);
+            g.keyed = 0;
+            g.pad_k = 0;
+            g.dchunk0 = (int32_t)dec.size();
+            g.dchunk_rows = 0;
+            pack_begin.push_back((int32_t)pack.size());
+            dec_begin.push_back((int32_t)dec.size());
+            static_assert(ARCTOPK_PACK_CHUNK % 8 == 0 && ARCTOPK_DEC_CHUNK % 8 == 0, "dense chunks keep alignment");
+            for (int64_t e = 0; e < s.n; e += pack_elems)
+                pack.push_back(Chunk{(int32_t)i, kChunkDense, e, std::min<int64_t>(pack_elems, s.n - e)});
+            for (int64_t e = 0; e < s.n; e += dec_elems)
+                dec_dense.push_back(Chunk{(int32_t)i, kChunkDense, e, std::min<int64_t>(dec_elems, s.n - e)});
+            continue;
+        }
         if (s.n <= small_cap) {
             small_ids.push_back((int32_t)i);
             small_rows = std::max<int64_t>(small_rows, s.n);
@@ -265,6 +293,13 @@ extern "C" int arctopk_plan_create(const int64_t* dims, const int32_t* ndims, in
         }
     }
 
+    // the decode table: every other segment's chunks, then the DENSE segments' (a stand-alone decode
+    // runs the two ranges as two launches, a riding decode the whole table)
+    ddec_begin.push_back((int32_t)dec_dense.size());
+    const int32_t n_dec_sparse = (int32_t)dec.size();
+    for (int32_t& b : ddec_begin) b += n_dec_sparse;
+    dec.insert(dec.end(), dec_dense.begin(), dec_dense.end());
+
     hipError_t e = hipSetDevice(device);
     if (e != hipSuccess) return (int)e;
     arctopk_plan* p = new (std::nothrow) arctopk_plan;
@@ -274,6 +309,8 @@ extern "C" int arctopk_plan_create(const int64_t* dims, const int32_t* ndims, in
     p->dtype = dtype;
     p->r = r;
     p->ratio = compress_ratio;
+    p->flags = flags;
+    p->n_dense = (int)dense_ids.size();
     p->nseg = (int)segs.size();
     p->info = info;
     p->h_segs = new arctopk_segment[segs.size()];
@@ -283,7 +320,9 @@ extern "C" int arctopk_plan_create(const int64_t* dims, const int32_t* ndims, in
     p->n_pack = (int)pack.size();
     p->n_dec = (int)dec.size();
     pack_begin.push_back((int32_t)pack.size());
-    dec_begin.push_back((int32_t)dec.size());
+    dec_begin.push_back(n_dec_sparse);
+    p->h_ddec_begin = new int32_t[ddec_begin.size()];
+    std::copy(ddec_begin.begin(), ddec_begin.end(), p->h_ddec_begin);
     p->h_pack_begin = new int32_t[pack_begin.size()];
     p->h_dec_begin = new int32_t[dec_begin.size()];
     std::copy(pack_begin.begin(), pack_begin.end(), p->h_pack_begin);
@@ -326,6 +365,7 @@ extern "C" int arctopk_plan_create(const int64_t* dims, const int32_t* ndims, in
     ALLOC_COPY(p->d_small, small_ids);
     ALLOC_COPY(p->d_large, large_ids);
     ALLOC_COPY(p->d_split, split_ids);
+    ALLOC_COPY(p->d_dense, dense_ids);
     p->n_split = (int)split_ids.size();
     p->split_rows_max = split_rows_max;
     if (part_len > 0) {
@@ -369,7 +409,8 @@ extern "C" int arctopk_plan_create(const int64_t* dims, const int32_t* ndims, in
         std::vector<VDraw> vd(segs.size());
         int nvd = 0;
         uint64_t adv = 0;
-        const int ve = vdraw_table(segs.data(), (int)segs.size(), r, device, vd.data(), &nvd, &adv);
+        const int ve = vdraw_table(segs.data(), (int)segs.size(), r, device, vd.data(), &nvd, &adv,
+                                   (flags & ARCTOPK_PLAN_RESTART_DRAWS) != 0);
         if (ve) { arctopk_plan_destroy(p); return ve; }
         vd.resize(nvd);
         p->n_vdraw = nvd;
@@ -391,9 +432,9 @@ extern "C" int arctopk_plan_create(const int64_t* dims, const int32_t* ndims, in
 }
 
 // A plan over segments [seg_begin, seg_end) of `parent` (a group of consecutive tensors of the
-// bucket): its own work tables, the parent's geometry and projection draws.  A tensor's
-// geometry depends on (kind, n, m) only, so each segment is planned as a [n] (RAW) or [n, m]
-// (SKETCH) tensor; the draw table keeps the parent's Philox offsets (a tensor's V is the one
+// bucket): its own work tables, the parent's geometry, plan flags and projection draws.  A tensor's
+// geometry depends on (kind, n, m) only, so each segment is planned as a [n] (RAW, or DENSE under
+// the parent's flags) or [n, m] (SKETCH) tensor; the draw table keeps the parent's Philox offsets (a tensor's V is the one
 // the whole bucket's draw gives it), with V offsets relative to the group's first SKETCH tensor.
 // The group's offsets differ from the parent's by the group's base offsets, which must keep
 // every alignment the kernels test (16-B units: multiples of 8 elements).
@@ -417,8 +458,8 @@ extern "C" int arctopk_plan_group(const arctopk_plan* parent, int32_t seg_begin,
         nd.push_back(s.kind == ARCTOPK_SEG_SKETCH ? 2 : 1);
     }
     arctopk_plan* c = nullptr;
-    int e = arctopk_plan_create(dims.data(), nd.data(), (int32_t)nd.size(), parent->r, parent->ratio,
-                                parent->dtype, parent->device, &c);
+    int e = arctopk_plan_create_ex(dims.data(), nd.data(), (int32_t)nd.size(), parent->r, parent->ratio,
+                                   parent->dtype, parent->device, parent->flags, &c);
     if (e) return e;
     for (int i = seg_begin; i < seg_end; ++i) {  // same geometry, offsets shifted by the base
         const arctopk_segment& s = parent->h_segs[i];
@@ -436,7 +477,8 @@ extern "C" int arctopk_plan_group(const arctopk_plan* parent, int32_t seg_begin,
     std::vector<VDraw> vd(parent->nseg);
     int nvd = 0;
     uint64_t adv = 0;
-    e = vdraw_table(parent->h_segs, parent->nseg, parent->r, parent->device, vd.data(), &nvd, &adv);
+    e = vdraw_table(parent->h_segs, parent->nseg, parent->r, parent->device, vd.data(), &nvd, &adv,
+                    (parent->flags & ARCTOPK_PLAN_RESTART_DRAWS) != 0);
     if (e) { arctopk_plan_destroy(c); return e; }
     std::vector<VDraw> mine;
     for (int i = 0, j = 0; i < parent->nseg; ++i) {
@@ -474,12 +516,19 @@ extern "C" int arctopk_plan_group(const arctopk_plan* parent, int32_t seg_begin,
 extern "C" int arctopk_plan_describe(const int64_t* dims, const int32_t* ndims, int32_t ntensors,
                                      int32_t r, double compress_ratio, arctopk_segment* segs_out,
                                      arctopk_plan_info* info) {
+    return arctopk_plan_describe_ex(dims, ndims, ntensors, r, compress_ratio, 0, segs_out, info);
+}
+
+extern "C" int arctopk_plan_describe_ex(const int64_t* dims, const int32_t* ndims, int32_t ntensors,
+                                        int32_t r, double compress_ratio, int32_t flags,
+                                        arctopk_segment* segs_out, arctopk_plan_info* info) {
     if (!dims || !ndims || !info || ntensors < 1) return ARCTOPK_EINVAL;
+    if (flags & ~(ARCTOPK_PLAN_DENSE_1D | ARCTOPK_PLAN_RESTART_DRAWS)) return ARCTOPK_EINVAL;
     if (r < 1 || r > kMaxR) return ARCTOPK_EINVAL;
     if (!(compress_ratio > 0.0) || compress_ratio > 1.0) return ARCTOPK_EINVAL;
     std::vector<arctopk_segment> segs;
     std::memset(info, 0, sizeof(*info));
-    int st = build_segments(dims, ndims, ntensors, r, compress_ratio, segs, *info);
+    int st = build_segments(dims, ndims, ntensors, r, compress_ratio, flags, segs, *info);
     if (st) return st;
     if (segs_out) std::copy(segs.begin(), segs.end(), segs_out);
     return 0;
@@ -500,6 +549,7 @@ extern "C" int arctopk_plan_destroy(arctopk_plan* p) {
     if (p->d_small) (void)hipFree(p->d_small);
     if (p->d_large) (void)hipFree(p->d_large);
     if (p->d_split) (void)hipFree(p->d_split);
+    if (p->d_dense) (void)hipFree(p->d_dense);
     if (p->d_part) (void)hipFree(p->d_part);
     delete[] p->h_segs;
     delete[] p->h_pack_begin;
@@ -515,6 +565,7 @@ extern "C" int arctopk_plan_destroy(arctopk_plan* p) {
     if (p->d_vdraw) (void)hipFree(p->d_vdraw);
     if (p->d_vchunk) (void)hipFree(p->d_vchunk);
     delete[] p->h_dec_begin;
+    delete[] p->h_ddec_begin;
     delete p;
     return 0;
 }

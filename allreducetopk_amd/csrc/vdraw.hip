@@ -19,9 +19,12 @@ __global__ void __launch_bounds__(256) k_draw_v(const VDraw* __restrict__ segs,
 
 namespace arctopk {
 
-// host: the draw table of a plan's SKETCH segments (torch's launch geometry on `device`)
+// host: the draw table of a plan's SKETCH segments (torch's launch geometry on `device`).
+// restart: every tensor is drawn by a fresh generator seeded with the call's seed
+// (group_topk_hook_no_reshape_c4.py:31-39): Philox offset 0 each, and the global generator's
+// offset does not move
 int vdraw_table(const arctopk_segment* segs, int nseg, int r, int device, VDraw* out, int* nout,
-                uint64_t* advance) {
+                uint64_t* advance, bool restart) {
     int sms = 0, maxthr = 0;
     hipError_t e = hipDeviceGetAttribute(&sms, hipDeviceAttributeMultiprocessorCount, device);
     if (e == hipSuccess) e = hipDeviceGetAttribute(&maxthr, hipDeviceAttributeMaxThreadsPerMultiProcessor, device);
@@ -38,13 +41,13 @@ int vdraw_table(const arctopk_segment* segs, int nseg, int r, int device, VDraw*
         d.v_off = segs[i].v_off;
         d.numel = (int64_t)numel;
         d.stride = stride;
-        d.offset = off;
+        d.offset = restart ? 0 : off;
         uint64_t inc = ((numel - 1) / (stride * 4) + 1) * 4;
         inc = (inc + 3) / 4 * 4;  // philox_cuda_state rounds the increment to a multiple of 4
         off += inc;
     }
     *nout = n;
-    *advance = off;
+    *advance = restart ? 0 : off;
     return 0;
 }
 

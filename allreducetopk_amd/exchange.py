@@ -178,6 +178,14 @@ class Comm:
             if old is None or t.numel() > old.numel() or t.dtype != old.dtype:
                 self._views[t.data_ptr()] = t
 
+    def unregister(self, t: torch.Tensor) -> None:
+        """Forget every registered view into `t`'s storage (a replaced plan's buffer and its
+        exchange groups' slices of it), so the buffer can be freed."""
+        if self._fn is not None:
+            base = t.untyped_storage().data_ptr()
+            for k in [k for k, v in self._views.items() if v.untyped_storage().data_ptr() == base]:
+                del self._views[k]
+
     def known_stream(self, s: "torch.cuda.Stream") -> None:
         """A stream the native step may hand the callback (found by its raw handle)."""
         self._streams[s.cuda_stream] = s

@@ -62,13 +62,24 @@ extern "C" {
 /* segment kinds */
 #define ARCTOPK_SEG_RAW 0     /* 1-D tensor: the "sketch" is the tensor itself (ref :19-41) */
 #define ARCTOPK_SEG_SKETCH 1  /* 2-D [n,m] or ND reshaped to [d/m, m], m = 2*t^2 (ref :44-102) */
+#define ARCTOPK_SEG_DENSE 2   /* 1-D tensor of a plan with ARCTOPK_PLAN_DENSE_1D: not compressed -- no
+                                 sketch, no select, every element ("row", m = 1) selected
+                                 (group_topk_hook_no_reshape_c4.py:19-25) */
+
+/* plan flags (arctopk_plan_create_ex): the reference's c4 variant of the hook
+ * (comm_hooks/group_topk_hook_no_reshape_c4.py) */
+#define ARCTOPK_PLAN_DENSE_1D 1       /* 1-D tensors are DENSE segments instead of RAW ones */
+#define ARCTOPK_PLAN_RESTART_DRAWS 2  /* device projections: every SKETCH tensor's V is drawn from
+                                         Philox offset 0 of the call's seed (a fresh generator per
+                                         tensor, c4 :31-39, :70-77) instead of one advancing stream */
 
 typedef struct arctopk_plan arctopk_plan;
 
 /* Totals of a plan, for sizing the caller's buffers. */
 typedef struct {
     int64_t numel;       /* bucket elements (bucket.buffer().numel())                  */
-    int64_t sketch_len;  /* floats of the concatenated sketch: sum n*r (SKETCH) + d (RAW) */
+    int64_t sketch_len;  /* floats of the concatenated sketch: sum n*r (SKETCH) + d (RAW);
+                            DENSE segments add nothing (0: no sketch all-reduce, no select)  */
     int64_t v_len;       /* floats of the concatenated projections: sum m*r over SKETCH   */
     int64_t packed_len;  /* floats of the packed buffer: every segment's k_rows*m values,
                             each segment starting 16-B aligned (<= 3 pad floats between)  */
@@ -83,13 +94,13 @@ typedef struct {
 typedef struct {
     int64_t offset;      /* element offset in the bucket                 */
     int64_t n, m;        /* rows, columns (m = 1 for RAW)                 */
-    int64_t k_rows;      /* selected rows: max(1, int(n * ratio))  (ref cal_k :173-187) */
+    int64_t k_rows;      /* selected rows: max(1, int(n * ratio))  (ref cal_k :173-187); DENSE: n */
     int64_t sketch_off;  /* float offset in the sketch buffer            */
-    int64_t v_off;       /* float offset in the projection buffer (-1: RAW) */
+    int64_t v_off;       /* float offset in the projection buffer (-1: RAW, DENSE) */
     int64_t packed_off;  /* element offset in the packed buffer          */
     int64_t row_off;     /* offset in the slot map (global row index)    */
     int64_t sel_off;     /* offset in the selected-row list              */
-    int32_t kind;        /* ARCTOPK_SEG_RAW / ARCTOPK_SEG_SKETCH          */
+    int32_t kind;        /* ARCTOPK_SEG_RAW / ARCTOPK_SEG_SKETCH / ARCTOPK_SEG_DENSE */
     int32_t pad;
 } arctopk_segment;
 
@@ -102,10 +113,30 @@ typedef struct {
  */
 int arctopk_plan_create(const int64_t* dims, const int32_t* ndims, int32_t ntensors, int32_t r,
                         double compress_ratio, int32_t dtype, int32_t device, arctopk_plan** out);
+/*
+ * arctopk_plan_create with plan flags (ARCTOPK_PLAN_*; 0: arctopk_plan_create).  With
+ * ARCTOPK_PLAN_DENSE_1D a 1-D tensor is a DENSE segment: n = numel, m = 1, k_rows = n, v_off = -1;
+ * it adds nothing to sketch_len and n to values_len / packed_len / sel_rows / rows_total.  It
+ * has no encode work: arctopk_encode leaves its range of E untouched, and EF14's X = G + E
+ * (err_in of the plan's last arctopk_encode; else X = G) is formed by the pack, which therefore
+ * needs `grad` for EF14 too.  The select leaves the identity in its row list and slot map ranges
+ * (written once per binding of the plan's buffers, and by every select on other buffers); pack
+ * and decode stream it straight through, every element selected, without reading either:
+ *   NONE : packed = G                          out = mean(packed)
+ *   EF14 : packed = G + E, E := 0              out = mean(packed)
+ *   EF21 : D = G - E; packed = D; E += D       out = gE + mean(packed); gE := out
+ * Replaces: the c4 hook's 1-D branch (group_topk_hook_no_reshape_c4.py:19-25, cal_k :206-207).
+ */
+int arctopk_plan_create_ex(const int64_t* dims, const int32_t* ndims, int32_t ntensors, int32_t r,
+                           double compress_ratio, int32_t dtype, int32_t device, int32_t flags,
+                           arctopk_plan** out);
 int arctopk_plan_destroy(arctopk_plan* plan);
 /* Host-only: the geometry a plan would have (no device memory touched); segs_out may be NULL. */
 int arctopk_plan_describe(const int64_t* dims, const int32_t* ndims, int32_t ntensors, int32_t r,
                           double compress_ratio, arctopk_segment* segs_out, arctopk_plan_info* info);
+int arctopk_plan_describe_ex(const int64_t* dims, const int32_t* ndims, int32_t ntensors, int32_t r,
+                             double compress_ratio, int32_t flags, arctopk_segment* segs_out,
+                             arctopk_plan_info* info);
 int arctopk_plan_query(const arctopk_plan* plan, arctopk_plan_info* info);
 /*
  * A plan over the consecutive segments [seg_begin, seg_end) of `parent` (a group of the bucket's
@@ -113,7 +144,7 @@ int arctopk_plan_query(const arctopk_plan* plan, arctopk_plan_info* info);
  * projections (the parent's Philox offsets) are the parent's; every offset is relative to the
  * group's first segment, so bind the group to the parent's buffers at those segment's offsets
  * (sketch_off, row_off, row_off, packed_off, first SKETCH v_off) and pass bucket / residual
- * pointers at its element offset.  ARCTOPK_EINVAL when the group's base offsets are not
+ * pointers at its element offset.  The group inherits the parent's plan flags.  ARCTOPK_EINVAL when the group's base offsets are not
  * multiples of 8 elements (sketch, packed, bucket, V) and 4 (slot map), which keeps every vector
  * path of the kernels aligned as in the parent.  Destroy with arctopk_plan_destroy.
  * Replaces: nothing in the reference (its per-tensor sketch all-reduce, :33, :58, :88, is the
@@ -541,6 +572,9 @@ int arctopk_ef14_fold(const void* x, void* E, int64_t numel, int32_t err_in, int
  * torch's Philox4x32-10 normal_ kernel (hiprand) reproduced element by element, bit for bit.
  * Stream-ordered, one launch.  arctopk_plan_philox_advance: the device generator's Philox
  * offset after those draws (what torch.manual_seed + the reference's draws leave behind).
+ * On a plan with ARCTOPK_PLAN_RESTART_DRAWS every tensor's V starts at Philox offset 0 of `seed`
+ * (torch.empty(m, r, device=dev).normal_(generator=g), g a fresh device generator seeded with
+ * `seed`, c4 :31-39) and the advance is 0: the global generator is not drawn from.
  */
 int arctopk_draw_projections(const arctopk_plan* plan, uint64_t seed, void* V, void* stream);
 int arctopk_plan_philox_advance(const arctopk_plan* plan, uint64_t* advance);
