@@ -19,6 +19,7 @@ LIB_PATH = LIB_OVERRIDE or os.path.join(PKG, "lib", "libarctopk.so")
 
 EF_NONE, EF14, EF21 = 0, 1, 2
 EF_CODE = {"noef": EF_NONE, "ef14": EF14, "ef21": EF21}
+ERR_IN_NONE, ERR_IN_READ, ERR_IN_ZERO_ROWS = 0, 1, 2  # ARCTOPK_ERR_IN_* (EF14's err_in)
 EINVAL = 1001  # ARCTOPK_EINVAL
 SEG_RAW, SEG_SKETCH, SEG_DENSE = 0, 1, 2
 PLAN_DENSE_1D, PLAN_RESTART_DRAWS = 1, 2  # ARCTOPK_PLAN_* flags (arctopk_plan_create_ex)
@@ -70,6 +71,7 @@ _SIGS = {
     "arctopk_select": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "arctopk_select_draw": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
                                       c_uint64, c_void_p, c_void_p]),
+    "arctopk_diag_zero_row_encodes": (c_int32, [c_void_p, ctypes.POINTER(c_int64)]),
     "arctopk_plan_bind": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "arctopk_step": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
                                c_uint64, c_void_p, c_uint64, c_void_p, c_void_p]),

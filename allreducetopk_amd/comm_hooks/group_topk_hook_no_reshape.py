@@ -533,6 +533,40 @@ class GroupTopKState(HookState):
         self.predraw_hits = 0
         self._succ: Dict[int, int] = {}  # bucket -> the bucket that followed it last time
         self._last_b = None
+        # EF14 zero rows: the previous compressed call of a bucket left
+        # every row it selected all zeros in the residual, so this call's encode need not read them
+        # back (err_in = 2, N.ERR_IN_ZERO_ROWS).  The hook vouches for the residual: per bucket, the
+        # plan, the residual tensor, its data_ptr() and _version and the slot map's _version as the
+        # last whole-bucket EF14 step left them; anything else (a torch in-place op on the residual,
+        # another plan, a reload, an exception) passes err_in = 1 for one call.  The native kernels
+        # write through raw pointers and bump no _version; the library keeps its own record of the
+        # slot map, the pack or finalize and its stream (include/arctopk.h, arctopk_encode).
+        self.err_zero_rows = os.environ.get("ARCTOPK_ERR_ZERO_ROWS", "1") != "0"
+        self._zr: Dict[int, tuple] = {}
+
+    def residual_touched(self, b=None) -> None:
+        """Tell the hook that bucket b's residual (None: every bucket's) was modified other than
+        by a torch op on ``error_dict[b]`` itself (which the hook sees): a kernel of the caller's
+        writing through its pointer, a view taken before.  The bucket's next call reads the whole
+        residual."""
+        if b is None:
+            self._zr.clear()
+        else:
+            self._zr.pop(int(b), None)
+
+    def _zr_take(self, b: int, plan, err, ef: int) -> bool:
+        """Whether this call may pass err_in = 2 for bucket b; the record is consumed (a call that
+        raises leaves none)."""
+        rec = self._zr.pop(b, None)
+        if rec is None or not self.err_zero_rows or ef != N.EF14 or err is None:
+            return False
+        p, e, ptr, ver, sver = rec
+        return (p is plan and e is err and err.data_ptr() == ptr and err._version == ver
+                and plan.slotmap._version == sver)
+
+    def _zr_note(self, b: int, plan, err) -> None:
+        """After a whole-bucket EF14 step of `plan` on residual `err` was enqueued."""
+        self._zr[b] = (plan, err, err.data_ptr(), err._version, plan.slotmap._version)
 
     @property
     def rng(self) -> torch.Generator:
@@ -668,6 +702,7 @@ class GroupTopKState(HookState):
     def _after_load(self) -> None:
         # prefetched projections were keyed on seeds of the old rng position
         self._proj.reset()
+        self._zr.clear()  # other residual tensors
 
     def _plan_for(self, bucket, buf=None) -> BucketPlan:
         if buf is None:
@@ -1103,6 +1138,8 @@ def group_topk_hook(state: GroupTopKState, bucket: dist.GradBucket
     sid = _current_raw_stream(dix)
     dtype = input_tensor.dtype
     L = _LIB[0]
+    # EF14: may this call skip the rows its previous call zeroed?  (consumes the bucket's record)
+    zr = state._zr_take(b, plan, err, ef)
     if not state.host_staged:
         # ONE native call per bucket (arctopk_exchange_step): the kernels, the collectives at
         # world size > 1 (or with force_exchange: the N > 1 code path over one-rank
@@ -1248,7 +1285,9 @@ def group_topk_hook(state: GroupTopKState, bucket: dist.GradBucket
             else:  # (most calls: no ctypes arrays built per call)
                 fin_plans = fin_marks = None
             _ht("prep")
-            st_ = L.arctopk_exchange_step(u.handle, u_x, u_e, u_g, ef, int(err_in), int(u_draw), seed,
+            # (groups of a bucket: plans of their own, whose last steps this record does not cover)
+            u_err_in = N.ERR_IN_ZERO_ROWS if (zr and err_in and not grouped) else int(err_in)
+            st_ = L.arctopk_exchange_step(u.handle, u_x, u_e, u_g, ef, u_err_in, int(u_draw), seed,
                                           u_next.handle if u_next is not None else None, u_nseed,
                                           sk.handle if comms else None, pk.handle if comms else None, sid,
                                           ars.cuda_stream if ars is not None else None,
@@ -1270,6 +1309,8 @@ def group_topk_hook(state: GroupTopKState, bucket: dist.GradBucket
             nplan.v_drawn, nplan.v_stream = nseed, sid
         if vslot >= 0:
             plan.projection_consumed(vslot, torch.cuda.current_stream(dev))
+        if ef == N.EF14 and not grouped:
+            state._zr_note(b, plan, err)
         _ht("native_step")
         state.comm_bits_this_round += 2 * (world_size - 1) * plan.bits_sum  # (:278)
         state.maybe_increase_iter(bucket)

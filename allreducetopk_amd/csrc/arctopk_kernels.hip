@@ -114,12 +114,17 @@ __device__ __forceinline__ float energy_regs(const float (&acc)[R]) {
     return rnd<T>(s);
 }
 
-template <typename T, int R, int EF, bool ERR_IN, bool ROWS = true>
+// ZR (EF14 with E, err_in = ARCTOPK_ERR_IN_ZERO_ROWS): every row `zmap` (the plan's slot map)
+// marks selected (slot >= 0) is all zeros in E; the ENC_ROW_VEC tiles issue no loads from E for
+// such a row and add a register zero instead (the add itself stays: -0.0 in G comes out +0.0, as
+// adding the stored zero gives).  Every other tile mode reads E as without ZR.
+template <typename T, int R, int EF, bool ERR_IN, bool ROWS = true, bool ZR = false>
 __device__ __forceinline__ void encode_tile(const SegDev* __restrict__ segs, const EncTile t,
                                             const T* __restrict__ G, T* __restrict__ E,
                                             const T* __restrict__ V, T* __restrict__ sketch,
                                             float* __restrict__ part_buf, uint32_t* __restrict__ keys,
-                                            float* __restrict__ lds) {
+                                            float* __restrict__ lds, const int32_t* __restrict__ zmap = nullptr) {
+    static_assert(!ZR || (EF == ARCTOPK_EF14 && ERR_IN && ROWS), "zero rows: EF14 with a residual, row tiles");
     const SegDev s = segs[t.seg];
     // keys mode (world size 1, multi-block select items): the row's energy key instead of its
     // sketch -- the key the select's key pass would form from the sketch (k_arc_keys)
@@ -252,6 +257,31 @@ __device__ __forceinline__ void encode_tile(const SegDev* __restrict__ segs, con
     // of one j).  Column-split tensors write per-part partial sketches, summed in fixed
     // part order by k_sketch_combine.
     const int c0 = t.c0, cl = t.clen;
+    // ZR: the slot-map entries of this wave's rows (q = wave + 4 i), 64 rows per lookup, one per lane,
+    // as a wave-uniform mask; the first lookup is in flight during the V^T staging below
+    uint64_t zmask = 0;
+    int zgrp = 0;
+    auto zlookup = [&](int grp) -> uint64_t {
+        const int64_t q = wave + 4 * ((int64_t)grp * 64 + lane);
+        int32_t slot = -1;
+        if (q < t.nrows) slot = zmap[s.row_off + t.row0 + q * t.rstride];
+        return __ballot(slot >= 0);
+    };
+    if constexpr (ZR) {
+        if (t.mode == ENC_ROW_VEC) zmask = zlookup(0);
+    }
+    // is tile row q of this wave marked?  (asked in the order the wave walks its rows)
+    auto zrow = [&](int64_t q) -> bool {
+        if constexpr (!ZR) return false;
+        else {
+            const int i = (int)((q - wave) >> 2);
+            if ((i >> 6) != zgrp) {
+                zgrp = i >> 6;
+                zmask = zlookup(zgrp);
+            }
+            return (zmask >> (i & 63)) & 1;
+        }
+    };
     // bf16 rows: V^T kept as bf16 pairs, X used as the packed bf16 words it is stored as, and
     // the sketch formed by v_dot2c_f32_bf16 (two products, exact in fp32, per instruction):
     // no unpacking of X and half the VALU instructions of the fp32-FMA form
@@ -299,9 +329,20 @@ __device__ __forceinline__ void encode_tile(const SegDev* __restrict__ segs, con
             float acc[R];
 #pragma unroll
             for (int j = 0; j < R; ++j) acc[j] = 0.f;
-            auto issue = [&](u4_t (&gx)[U], u4_t (&ex)[U], int64_t r_, int st_) {
+            auto issue = [&](u4_t (&gx)[U], u4_t (&ex)[U], int64_t r_, int st_, bool z_ = false) {
                 const T* gp = G + s.offset + r_ * m + c0;
                 const T* ep = E + s.offset + r_ * m + c0;
+                if constexpr (ZR) {
+                    if (z_) {  // (wave-uniform: one branch around the whole step's E loads)
+#pragma unroll
+                        for (int u = 0; u < U; ++u) {
+                            const int c = min(st_ * 64 * U + u * 64 + lane, mu - 1);
+                            gx[u] = ld16raw<T, true>(gp, c);
+                            ex[u] = u4_t{0u, 0u, 0u, 0u};
+                        }
+                        return;
+                    }
+                }
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     const int c = min(st_ * 64 * U + u * 64 + lane, mu - 1);
@@ -365,18 +406,18 @@ __device__ __forceinline__ void encode_tile(const SegDev* __restrict__ segs, con
             const int64_t nq = t.nrows;
             int64_t qa = wave;
             int sa = 0;
-            if (qa < nq) issue(ga, ea, t.row0 + qa * rs, sa);
+            if (qa < nq) issue(ga, ea, t.row0 + qa * rs, sa, zrow(qa));
             while (qa < nq) {
                 int64_t qb = qa;
                 int sb = sa + 1;
                 if (sb == steps) { sb = 0; qb += 4; }
-                if (qb < nq) issue(gb, eb, t.row0 + qb * rs, sb);
+                if (qb < nq) issue(gb, eb, t.row0 + qb * rs, sb, zrow(qb));
                 consume(ga, ea, t.row0 + qa * rs, sa);
                 if (qb >= nq) break;
                 qa = qb;
                 sa = sb + 1;
                 if (sa == steps) { sa = 0; qa += 4; }
-                if (qa < nq) issue(ga, ea, t.row0 + qa * rs, sa);
+                if (qa < nq) issue(ga, ea, t.row0 + qa * rs, sa, zrow(qa));
                 consume(gb, eb, t.row0 + qb * rs, sb);
             }
             return;
@@ -406,9 +447,21 @@ __device__ __forceinline__ void encode_tile(const SegDev* __restrict__ segs, con
 #pragma unroll
         for (int j = 0; j < R; ++j) acc2[j] = f2_t{0.f, 0.f};
 
-        auto issue = [&](float4 (&gx)[U][PQ], float4 (&ex)[U][PQ], int64_t r_, int st_) {
+        auto issue = [&](float4 (&gx)[U][PQ], float4 (&ex)[U][PQ], int64_t r_, int st_, bool z_ = false) {
             const T* gp = G + s.offset + r_ * m + c0;
             const T* ep = E + s.offset + r_ * m + c0;
+            if constexpr (ZR) {
+                if (z_) {  // (wave-uniform: one branch around the whole step's E loads)
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        const int c = min(st_ * 64 * U + u * 64 + lane, mu - 1);
+                        ld16<T, kEncNtLoad>(gp, c, gx[u]);
+#pragma unroll
+                        for (int h = 0; h < PQ; ++h) ex[u][h] = make_float4(0.f, 0.f, 0.f, 0.f);
+                    }
+                    return;
+                }
+            }
 #pragma unroll
             for (int u = 0; u < U; ++u) {  // unconditional (clamped) loads: no exec-masked blocks
                 const int c = min(st_ * 64 * U + u * 64 + lane, mu - 1);
@@ -493,18 +546,18 @@ __device__ __forceinline__ void encode_tile(const SegDev* __restrict__ segs, con
         const int64_t nq = t.nrows;
         int64_t qa = wave;
         int sa = 0;
-        if (qa < nq) issue(ga, ea, t.row0 + qa * rs, sa);
+        if (qa < nq) issue(ga, ea, t.row0 + qa * rs, sa, zrow(qa));
         while (qa < nq) {
             int64_t qb = qa;
             int sb = sa + 1;
             if (sb == steps) { sb = 0; qb += 4; }
-            if (qb < nq) issue(gb, eb, t.row0 + qb * rs, sb);
+            if (qb < nq) issue(gb, eb, t.row0 + qb * rs, sb, zrow(qb));
             consume(ga, ea, t.row0 + qa * rs, sa);
             if (qb >= nq) break;
             qa = qb;
             sa = sb + 1;
             if (sa == steps) { sa = 0; qa += 4; }
-            if (qa < nq) issue(ga, ea, t.row0 + qa * rs, sa);
+            if (qa < nq) issue(ga, ea, t.row0 + qa * rs, sa, zrow(qa));
             consume(gb, eb, t.row0 + qb * rs, sb);
         }
     } else {  // ENC_ROW_SCALAR
@@ -577,6 +630,52 @@ __global__ void __launch_bounds__(256) k_encode(const SegDev* __restrict__ segs,
         return;
     }
     encode_tile<T, R, EF, ERR_IN>(segs, tiles[blockIdx.x - pr.n], G, E, V, sketch, part_buf, keys, lds);
+}
+
+// k_encode<T, R, EF14, true> with the zero-rows skip (encode_tile, ZR): kernels of their own, so
+// the other encode kernels keep their code -- overloads of the name, so profiles count them with
+// the encode kernel they stand in for.  zmap: the plan's bound slot map.
+struct ZeroRows {};
+template <typename T, int R>
+__device__ __forceinline__ void encode_zr_block(const SegDev* __restrict__ segs, const EncTile* __restrict__ tiles,
+                                                const T* __restrict__ G, T* __restrict__ E,
+                                                const T* __restrict__ V, T* __restrict__ sketch,
+                                                float* __restrict__ part_buf, uint32_t* __restrict__ keys,
+                                                const PackRide<T>& pr, const int32_t* __restrict__ zmap,
+                                                float* __restrict__ lds) {
+    if ((int)blockIdx.x < pr.n) {
+        pack_chunk<T, ARCTOPK_EF14, false>(pr.segs, pr.chunks[blockIdx.x], pr.G, pr.E, pr.rowlist, pr.slotmap,
+                                           pr.packed, pr.dfirst, reinterpret_cast<int32_t*>(lds));
+        return;
+    }
+    encode_tile<T, R, ARCTOPK_EF14, true, true, true>(segs, tiles[blockIdx.x - pr.n], G, E, V, sketch, part_buf, keys,
+                                                      lds, zmap);
+}
+// fp32: 170 VGPRs, 2 waves per SIMD where k_encode<float, 4, EF14, true> has 3 (164) -- left so:
+// held to 168 registers for the third wave it measured slower
+// (the two are told apart by the order of their template parameters: plain names that every
+// profiler demangles)
+template <typename T, int R, typename Z>
+__global__ void __launch_bounds__(256) k_encode(const SegDev* __restrict__ segs,
+                                                const EncTile* __restrict__ tiles, int ntiles,
+                                                const T* __restrict__ G, T* __restrict__ E,
+                                                const T* __restrict__ V, T* __restrict__ sketch,
+                                                float* __restrict__ part_buf, uint32_t* __restrict__ keys,
+                                                PackRide<T> pr, const int32_t* __restrict__ zmap) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    encode_zr_block<T, R>(segs, tiles, G, E, V, sketch, part_buf, keys, pr, zmap, lds);
+}
+// bf16: 3 waves per SIMD asked for, as k_encode<bf16_t, 4, EF14, true> has (at 175 registers and 2
+// waves the bf16 headline lost 2 %; at 168 and 3 it gains)
+template <typename T, typename Z, int R>
+__global__ void __launch_bounds__(256, 3) k_encode(const SegDev* __restrict__ segs,
+                                                   const EncTile* __restrict__ tiles, int ntiles,
+                                                   const T* __restrict__ G, T* __restrict__ E,
+                                                   const T* __restrict__ V, T* __restrict__ sketch,
+                                                   float* __restrict__ part_buf, uint32_t* __restrict__ keys,
+                                                   PackRide<T> pr, const int32_t* __restrict__ zmap) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    encode_zr_block<T, R>(segs, tiles, G, E, V, sketch, part_buf, keys, pr, zmap, lds);
 }
 
 // The same for a tile table without wave-per-row tiles (only 1-D tensors and rows of m < 64:
@@ -3339,6 +3438,12 @@ inline void launch_done(void (*k)(KArgs...), dim3 grid, dim3 block, size_t lds, 
     else hipLaunchKernelGGL(k, grid, block, lds, st, args...);
 }
 
+// does this encode run the zero-rows kernel?  err_in 2 on an EF14 call whose residual, stream and
+// bound slot map the plan's record covers (common.h, zr_*)
+inline bool zero_rows(const arctopk_plan* p, const void* E, int ef, int err_in, int r, hipStream_t st) {
+    return ef == ARCTOPK_EF14 && err_in == ARCTOPK_ERR_IN_ZERO_ROWS && r == 4 && zr_holds(p, E, (void*)st);
+}
+
 // one launch (every tile's V slice fits in LDS), then the partial-sketch sums of
 // column-split tensors; done: completed by the last of them
 template <typename T, int R>
@@ -3385,6 +3490,16 @@ int launch_encode_r(const arctopk_plan* p, const T* G, T* E, int ef, int err_in,
                 launch_done(&k_encode_short<T, R, ARCTOPK_EF14, false>, grid, block, lds, st, enc_done, p->d_segs, tiles, nt, G, E, V, sk, pb, keys, pr);
             else
                 launch_done(&k_encode_short<T, R, ARCTOPK_EF21, true>, grid, block, lds, st, enc_done, p->d_segs, tiles, nt, G, E, V, sk, pb, keys, pr);
+        } else if (zero_rows(p, E, ef, err_in, R, st)) {
+            // err_in 2, vouched for by the plan's record: the marked rows of E are not read (r = 4
+            // only, both dtypes; other ranks, the lean kernel and carried steps run as err_in 1)
+            if constexpr (R == 4) {
+                if constexpr (sizeof(T) == 4)
+                    launch_done(&k_encode<T, R, ZeroRows>, grid, block, lds, st, enc_done, p->d_segs, tiles, nt, G, E, V, sk, pb, keys, pr, (const int32_t*)p->b_slotmap);
+                else
+                    launch_done(&k_encode<T, ZeroRows, R>, grid, block, lds, st, enc_done, p->d_segs, tiles, nt, G, E, V, sk, pb, keys, pr, (const int32_t*)p->b_slotmap);
+                const_cast<arctopk_plan*>(p)->zr_encodes += 1;
+            }
         } else if (ef == ARCTOPK_EF_NONE)
             launch_done(&k_encode<T, R, ARCTOPK_EF_NONE, false>, grid, block, lds, st, enc_done, p->d_segs, tiles, nt, G, E, V, sk, pb, keys, pr);
         else if (ef == ARCTOPK_EF14 && err_in)
@@ -3418,6 +3533,7 @@ int launch_encode(const arctopk_plan* p, const void* grad, void* err, int ef, in
     // DENSE segments have no encode tile: the step's pack (or fused pack + decode) forms EF14's
     // X = G + E itself, with this call's err_in (host bookkeeping of the plan, like x_*)
     const_cast<arctopk_plan*>(p)->dense_err_in = err_in;
+    if (ef != ARCTOPK_EF14) zr_clear(p);  // a step in another EF mode: the residual is not EF14's
     switch (p->r) {
         case 1: return launch_encode_r<T, 1>(p, G, E, ef, err_in, Vt, sk, keys, st, pr, done, er, er_lds, er_short);
         case 2: return launch_encode_r<T, 2>(p, G, E, ef, err_in, Vt, sk, keys, st, pr, done, er, er_lds, er_short);
@@ -3547,6 +3663,9 @@ int launch_select(const arctopk_plan* p, const void* sketch_, int32_t ws, int32_
                   bool keyed = false) {
     *drawn = false;
     if (rode) *rode = false;
+    // the bound row list / slot map rewritten: no longer the ones a pack or finalize zeroed E by
+    if (slotmap == p->b_slotmap || rowlist == p->b_rowlist) zr_clear(p);
+    zr_clear(p->x_carry);  // (its selects ride in this select's compact launch)
     const T* sketch = static_cast<const T*>(sketch_);
     // with large segments, the small segments' selects run inside the first batch's refine
     if (p->n_small && p->n_large_batches == 0) {
@@ -3648,6 +3767,7 @@ int launch_select(const arctopk_plan* p, const void* sketch_, int32_t ws, int32_
             if (e) return e;
             if (bi == 0) *drawn = true;
             if (take && rode) *rode = true;
+            if (take && dr.fin == 1) zr_set(ride->rp, ride->rp->x_err, (void*)st);
             continue;
         }
         static const hipError_t lds_ok = hipFuncSetAttribute(
@@ -3678,6 +3798,7 @@ int launch_select(const arctopk_plan* p, const void* sketch_, int32_t ws, int32_
                                          : launch_write_ride<T, ARCTOPK_EF_NONE>(p, bi, rowlist, slotmap, dr, shm, st);
             if (e) return e;
             if (rode) *rode = true;
+            if (dr.fin == 1) zr_set(ride->rp, ride->rp->x_err, (void*)st);
             continue;
         }
         e = ms_arc_write(b, p->d_large_batches + bi, p->d_keys, p->d_mws, p->mws_cap, rowlist, slotmap, st);
@@ -3721,7 +3842,11 @@ int launch_pack(const arctopk_plan* p, int c0, int c1, const void* grad_, void* 
                                      p->dense_err_in);
     else
         return ARCTOPK_EINVAL;
-    return (int)hipGetLastError();
+    const int e = (int)hipGetLastError();
+    // EF14's whole pack over the bound tables: every selected row of `err` is zero after it
+    if (!e && ef == ARCTOPK_EF14 && c0 == 0 && c1 == p->n_pack && rowlist == p->b_rowlist && slotmap == p->b_slotmap)
+        zr_set(p, err_, (void*)st);
+    return e;
 }
 
 // The mode-3 decode chunk table from a slot map alone (the public decode entry points): for
@@ -3825,7 +3950,10 @@ int launch_decode(const arctopk_plan* p, int c0, int c1, const int32_t* dfirst, 
     } else {
         decode_launch(&k_decode<T, ARCTOPK_EF_NONE>, d.n, lds, st, done, d);
     }
-    return (int)hipGetLastError();
+    const int e = (int)hipGetLastError();
+    // EF14's fused finalize (the whole plan, decode_signal): it zeroes the selected rows of E
+    if (!e && fin == 1 && slotmap == p->b_slotmap) zr_set(p, E, (void*)st);
+    return e;
 }
 
 }  // namespace
@@ -3887,6 +4015,7 @@ int encode_keyed(const arctopk_plan* p, const void* grad, void* err, int32_t ef,
         const int e = launch_encode<bf16_t>(p, grad, err, ef, err_in, V, sketch, keys, st, pr, (hipEvent_t)done, er,
                                             er_lds, p->x_carry ? p->x_carry->enc_short != 0 : true);
         if (!e && take) *rode = 1;
+        if (!e && take && ef == ARCTOPK_EF14) zr_set(rp, rp_err, stream);
         return e;
     }
     PackRide<float> pr{};
@@ -3898,6 +4027,7 @@ int encode_keyed(const arctopk_plan* p, const void* grad, void* err, int32_t ef,
     const int e = launch_encode<float>(p, grad, err, ef, err_in, V, sketch, keys, st, pr, (hipEvent_t)done, er, er_lds,
                                        p->x_carry ? p->x_carry->enc_short != 0 : true);
     if (!e && take) *rode = 1;
+    if (!e && take && ef == ARCTOPK_EF14) zr_set(rp, rp_err, stream);
     return e;
 }
 }  // namespace arctopk
@@ -3966,6 +4096,7 @@ int launch_select_ride(const arctopk_plan* p, const void* sketch_, int32_t ws, i
     if (dr.fin == 3) dr.fin = 0;
     dr.E = static_cast<T*>(rp->x_err);
     dr.dense_in = rp->dense_err_in;
+    if (slotmap == p->b_slotmap || rowlist == p->b_rowlist) zr_clear(p);
     const size_t shm = (size_t)std::max(p->small_lds, rp->dec_lds_bytes);
     const dim3 grid(p->n_small + dr.n + job.n);
     const T* sketch = static_cast<const T*>(sketch_);
@@ -3990,7 +4121,9 @@ int launch_select_ride(const arctopk_plan* p, const void* sketch_, int32_t ws, i
                           (const SegDev*)p->d_segs, (const int32_t*)p->d_small, p->n_small, sketch, (int)p->r,
                           make_scale(ws), rowlist, slotmap, dr, job);
     }
-    return (int)hipGetLastError();
+    const int e = (int)hipGetLastError();
+    if (!e && dr.fin == 1) zr_set(rp, rp->x_err, (void*)st);
+    return e;
 }
 }  // namespace
 
@@ -4154,7 +4287,10 @@ int launch_decode_pair(const RideArgs& a, const RideArgs& b, hipStream_t st, hip
         if (done) hipExtLaunchKernelGGL((k_decode2<T, ARCTOPK_EF_NONE>), grid, dim3(256), lds, st, nullptr, done, 0, da, db);
         else hipLaunchKernelGGL((k_decode2<T, ARCTOPK_EF_NONE>), grid, dim3(256), lds, st, da, db);
     }
-    return (int)hipGetLastError();
+    const int e = (int)hipGetLastError();
+    if (!e && da.fin == 1) zr_set(a.rp, a.rp->x_err, (void*)st);
+    if (!e && db.fin == 1) zr_set(b.rp, b.rp->x_err, (void*)st);
+    return e;
 }
 }  // namespace
 
@@ -4317,5 +4453,6 @@ extern "C" int arctopk_step(const arctopk_plan* p, void* bucket, void* err, void
     if (!e) e = step_mark(marks, ARCTOPK_MARK_PACK, st);
     if (!e) e = arctopk::decode_signal(p, p->b_packed, p->b_slotmap, 1, ef, gerr, bucket, st, nullptr);
     if (!e) e = step_mark(marks, ARCTOPK_MARK_DECODE, st);
+    if (e) zr_clear(p);  // a failed step: nothing is known of its residual
     return e;
 }

@@ -454,8 +454,33 @@ struct arctopk_plan {
     int x_t_ef, x_t_err_in;
     const arctopk_plan* x_carry;        // during an exchange step: the trailing plan its encode and
                                         //   compact launches carry (encode_keyed, launch_select)
+    // EF14 zero-rows record (err_in = ARCTOPK_ERR_IN_ZERO_ROWS): the bound slot map is the one this
+    // plan's last select wrote, and an EF14 pack or fused finalize over it has since been enqueued,
+    // zeroing every row it marks selected in residual zr_err -- on stream zr_stream (zr_join: a
+    // stream the library made wait for that work).  Any other writer of the bound row list or slot
+    // map clears it (zr_clear), the step's own select first.
+    int zr_valid;
+    void* zr_err;
+    void* zr_stream;
+    void* zr_join;
+    int64_t zr_encodes;                 // encode launches that ran the zero-rows kernels (diagnostics)
 };
 namespace arctopk {
+// host bookkeeping of the plan, like the exchange step's x_* fields
+inline void zr_clear(const arctopk_plan* p) {
+    if (p) const_cast<arctopk_plan*>(p)->zr_valid = 0;
+}
+inline void zr_set(const arctopk_plan* p, void* err, void* stream) {
+    arctopk_plan* q = const_cast<arctopk_plan*>(p);
+    q->zr_valid = err != nullptr;
+    q->zr_err = err;
+    q->zr_stream = stream;
+    q->zr_join = stream;
+}
+// an encode of residual `err` on `stream` may skip the marked rows' loads
+inline bool zr_holds(const arctopk_plan* p, const void* err, void* stream) {
+    return p->zr_valid && p->b_slotmap && err == p->zr_err && (stream == p->zr_stream || stream == p->zr_join);
+}
 // keyed: the call's encode ran in keys mode (encode_keyed; world size 1 only)
 int select_ride(const arctopk_plan* p, const void* sketch, int32_t ws, int32_t* rowlist, int32_t* slotmap,
                 const arctopk_plan* next, uint64_t next_seed, void* next_V, const arctopk_plan* rp,

@@ -591,6 +591,8 @@ int join_stream(arctopk_plan* p, hipStream_t from, hipStream_t to) {
     if (int e = ensure_event(&p->x_ev_join, hipEventDisableTiming | hipEventReleaseToDevice)) return e;
     hipError_t he = hipEventRecord((hipEvent_t)p->x_ev_join, from);
     if (he == hipSuccess) he = hipStreamWaitEvent(to, (hipEvent_t)p->x_ev_join, 0);
+    // (`to` is now ordered after a pack or finalize enqueued on `from`: zero-rows record)
+    if (he == hipSuccess && p->zr_valid && p->zr_stream == (void*)from) p->zr_join = (void*)to;
     return (int)he;
 }
 // the stream a deferred step's remaining work goes on: its select stream, else the caller's
@@ -628,6 +630,9 @@ extern "C" int arctopk_exchange_trail(arctopk_plan* p, void* bucket, void* err, 
         return ARCTOPK_EINVAL;
     if (ef == ARCTOPK_EF14 && !err) return ARCTOPK_EINVAL;
     if (p->x_trail || p->x_deferred) return ARCTOPK_EINVAL;  // the caller finishes a plan's step first
+    // a carried step's encode runs as err_in 1 and its select in the carrier's launches: the zero-rows
+    // record ends here (a step enqueued on its own sets it again)
+    arctopk::zr_clear(p);
     if (!V) V = p->b_V;
     if (draw && p->info.v_len > 0) {
         if (int e = arctopk_draw_projections(p, seed, const_cast<void*>(V), stream)) return e;
@@ -667,6 +672,14 @@ extern "C" int arctopk_exchange_finish(arctopk_plan* p, void* stream, void* cons
     return e;
 }
 
+namespace {
+int exchange_step(arctopk_plan* p, void* bucket, void* err, void* gerr, int32_t ef, int32_t err_in, int32_t draw,
+                  uint64_t seed, const arctopk_plan* next, uint64_t next_seed, arctopk_comm* sketch_comm,
+                  arctopk_comm* packed_comm, void* stream, void* ar_stream, int32_t defer, arctopk_plan* ride,
+                  void* const* ride_marks, arctopk_plan* const* finish, void* const* const* finish_marks,
+                  int32_t nfinish, const void* V, void* const* marks, void* sel_stream, arctopk_plan* trail);
+}  // namespace
+
 extern "C" int arctopk_exchange_step(arctopk_plan* p, void* bucket, void* err, void* gerr, int32_t ef,
                                      int32_t err_in, int32_t draw, uint64_t seed, const arctopk_plan* next,
                                      uint64_t next_seed, arctopk_comm* sketch_comm, arctopk_comm* packed_comm,
@@ -674,6 +687,24 @@ extern "C" int arctopk_exchange_step(arctopk_plan* p, void* bucket, void* err, v
                                      void* const* ride_marks, arctopk_plan* const* finish,
                                      void* const* const* finish_marks, int32_t nfinish, const void* V,
                                      void* const* marks, void* sel_stream, arctopk_plan* trail) {
+    const int e = exchange_step(p, bucket, err, gerr, ef, err_in, draw, seed, next, next_seed, sketch_comm, packed_comm,
+                                stream, ar_stream, defer, ride, ride_marks, finish, finish_marks, nfinish, V, marks,
+                                sel_stream, trail);
+    if (e) {  // a failed step: nothing is known of the residuals of the plans it touched
+        arctopk::zr_clear(p);
+        arctopk::zr_clear(ride);
+        arctopk::zr_clear(trail);
+        for (int32_t i = 0; finish && i < nfinish; ++i) arctopk::zr_clear(finish[i]);
+    }
+    return e;
+}
+
+namespace {
+int exchange_step(arctopk_plan* p, void* bucket, void* err, void* gerr, int32_t ef, int32_t err_in, int32_t draw,
+                  uint64_t seed, const arctopk_plan* next, uint64_t next_seed, arctopk_comm* sketch_comm,
+                  arctopk_comm* packed_comm, void* stream, void* ar_stream, int32_t defer, arctopk_plan* ride,
+                  void* const* ride_marks, arctopk_plan* const* finish, void* const* const* finish_marks,
+                  int32_t nfinish, const void* V, void* const* marks, void* sel_stream, arctopk_plan* trail) {
     if (!p || !bucket || !p->b_sketch || !sketch_comm != !packed_comm || nfinish < 0 || (nfinish && !finish))
         return ARCTOPK_EINVAL;
     if (trail && (trail == p || !trail->x_trail)) return ARCTOPK_EINVAL;
@@ -705,7 +736,7 @@ extern "C" int arctopk_exchange_step(arctopk_plan* p, void* bucket, void* err, v
     if (!e && trail) {
         constexpr int64_t big_rows = ARCTOPK_SEL_BIG_ROWS;
         const bool fits = !sketch_comm && !marks && trail->device == p->device && trail->dtype == p->dtype &&
-                          trail->r == p->r && p->r == 4 && trail->x_t_ef == ef && trail->x_t_err_in == err_in &&
+                          trail->r == p->r && p->r == 4 && trail->x_t_ef == ef && !trail->x_t_err_in == !err_in &&
                           ef != ARCTOPK_EF21 && p->n_large_batches > 0 && p->n_split == 0 &&
                           trail->n_large_batches == 0 && trail->n_small > 0 &&
                           trail->n_split == 0 && !trail->any_keyed && trail->small_lds <= big_rows * 4 + 16 &&
@@ -943,6 +974,14 @@ extern "C" int arctopk_exchange_step(arctopk_plan* p, void* bucket, void* err, v
     if (!e) e = join_stream(p, ss, st);  // the caller's stream sees the bucket decoded
     ht.lap(7);
     return e;
+}
+}  // namespace
+
+// Diagnostics: encode launches of `p` that ran the zero-rows kernel (err_in 2 accepted) so far
+extern "C" int arctopk_diag_zero_row_encodes(const arctopk_plan* p, int64_t* count) {
+    if (!p || !count) return ARCTOPK_EINVAL;
+    *count = p->zr_encodes;
+    return 0;
 }
 
 // Diagnostics (include/arctopk.h, diagnostics section): host ns spent in the exchange step's parts since the

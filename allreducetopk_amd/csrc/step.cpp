@@ -17,6 +17,7 @@ extern "C" int arctopk_plan_bind(arctopk_plan* p, void* sketch, int32_t* rowlist
     p->b_slotmap = slotmap;
     p->b_packed = packed;
     p->b_V = V;
+    arctopk::zr_clear(p);  // another slot map: nothing is known of the rows it marks
     p->dense_init = 0;  // the DENSE ranges of the new row list / slot map: by the next select
     return 0;
 }

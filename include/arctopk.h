@@ -52,6 +52,11 @@ extern "C" {
 #define ARCTOPK_EF_NONE 0
 #define ARCTOPK_EF14 1
 #define ARCTOPK_EF21 2
+/* err_in of the EF14 entry points: 0 the residual is all zeros and is not read (the first call),
+ * 1 it is read, 2 it is read except the rows the plan's last select chose (arctopk_encode) */
+#define ARCTOPK_ERR_IN_NONE 0
+#define ARCTOPK_ERR_IN_READ 1
+#define ARCTOPK_ERR_IN_ZERO_ROWS 2
 
 /* element types of a bucket (and of its sketch, projections and packed values, which
  * the reference keeps in the bucket's dtype: group_topk_hook_no_reshape.py:49, :263) */
@@ -159,6 +164,18 @@ int arctopk_plan_segment(const arctopk_plan* plan, int32_t i, arctopk_segment* s
  * K1 encode.  EF pre-apply fused with the rank-r sketch of every tensor.
  *   ef = NONE : X = G
  *   ef = EF14 : X = G + E (err_in = 1) or X = G (first call, err_in = 0); writes E := X
+ *               err_in = 2 (ARCTOPK_ERR_IN_ZERO_ROWS): as 1, and the caller states that `err` has not
+ *               been written since this plan's last EF14 pack or fused finalize (arctopk_pack,
+ *               arctopk_step, arctopk_exchange_step / _finish on the plan's bound buffers), which
+ *               left every row its select chose all zeros.  The library keeps its own record of that
+ *               pack or finalize: the residual pointer and the stream it was enqueued on, dropped by
+ *               anything else that writes the bound row list or slot map (arctopk_select,
+ *               arctopk_select_draw, arctopk_plan_bind, a step in another EF mode, a failed step).
+ *               Only if the record holds for `err`, and `stream` is that stream or one the library
+ *               made wait for it, the wave-per-row tiles (rows of >= 64 elements, r = 4) read the
+ *               bound slot map and issue no loads from E for the rows it marks (slot >= 0); X, E and
+ *               the sketch are bit for bit those of err_in = 1.  Otherwise, and for every other tile
+ *               kind, rank, carried trailing step and the sparse entry points, 2 means 1.
  *   ef = EF21 : X = G - E (nothing written but the sketch)
  * sketch[SKETCH seg] = X.view(n,m) @ V  ([n][r] row-major); sketch[RAW seg] = X.
  * `V` is the concatenation of each SKETCH tensor's [m][r] projection in bucket order.
@@ -216,6 +233,8 @@ int arctopk_select_draw(const arctopk_plan* plan, const void* sketch, int32_t wo
  * pack -> decode into `bucket`, on the buffers bound to the plan by arctopk_plan_bind (the
  * sketch, row list, slot map, packed values and projection buffer the phase entry points
  * take as arguments).  One foreign-function call per hook call instead of one per phase.
+ * err_in (EF14): 0, 1 or 2 (ARCTOPK_ERR_IN_ZERO_ROWS) with the meaning and the conditions given at
+ * arctopk_encode; the step's own pack is what sets the plan's zero-rows record for the next call.
  */
 int arctopk_plan_bind(arctopk_plan* plan, void* sketch, int32_t* rowlist, int32_t* slotmap,
                       void* packed, void* V);
@@ -329,6 +348,11 @@ int arctopk_comm_allreduce(arctopk_comm* comm, void* buf, int64_t count, int32_t
  *   selects as extra blocks of this step's first compact launch; otherwise it is enqueued on its
  *   own first.  Either way it leaves this call as a deferred step (its decode: a later `ride` /
  *   `finish` / arctopk_exchange_finish, like a defer = 1 step's).
+ * err_in (EF14): 0, 1 or 2 (ARCTOPK_ERR_IN_ZERO_ROWS) with the meaning and the conditions given at
+ *   arctopk_encode.  The record that 2 relies on is set by this plan's pack (with communicators)
+ *   or fused finalize (world size 1), on the stream it is enqueued on; a finalize that rides in a
+ *   later step's select on a select stream, a carried trailing step and the groups of a bucket
+ *   leave the next encode on the caller's stream to run as 1.
  * Replaces: the whole of group_topk_hook's compressed path (:254-290) given the seed.
  */
 int arctopk_exchange_step(arctopk_plan* plan, void* bucket, void* err, void* gerr, int32_t ef,
@@ -647,6 +671,9 @@ int arctopk_round_bf16(const float* in, uint16_t* out, int64_t n, void* stream);
  * pack, packed all-reduce, finish, decode; *calls = steps summed -- and the sums are reset.
  * All zero when the variable is unset.  (bench.py --host-timing breakdowns) */
 int arctopk_diag_host_times(int64_t* ns, int32_t n, int64_t* calls);
+/* Encode launches of `plan` so far that ran the zero-rows kernel (err_in = 2 accepted; see
+ * arctopk_encode).  Tests use it to show the path was taken or refused. */
+int arctopk_diag_zero_row_encodes(const arctopk_plan* plan, int64_t* count);
 
 /* library build identification (for smoke tests) */
 const char* arctopk_version(void);
