@@ -21,6 +21,7 @@ EF_NONE, EF14, EF21 = 0, 1, 2
 EF_CODE = {"noef": EF_NONE, "ef14": EF14, "ef21": EF21}
 ERR_IN_NONE, ERR_IN_READ, ERR_IN_ZERO_ROWS = 0, 1, 2  # ARCTOPK_ERR_IN_* (EF14's err_in)
 EINVAL = 1001  # ARCTOPK_EINVAL
+EDTYPE = 1003  # ARCTOPK_EDTYPE
 SEG_RAW, SEG_SKETCH, SEG_DENSE = 0, 1, 2
 PLAN_DENSE_1D, PLAN_RESTART_DRAWS = 1, 2  # ARCTOPK_PLAN_* flags (arctopk_plan_create_ex)
 F32 = 0
@@ -107,6 +108,8 @@ _SIGS = {
                                       POINTER(c_int64), POINTER(c_int64), c_void_p, c_void_p, c_void_p,
                                       c_int32, c_int32, c_void_p]),
     "arctopk_ef14_fold": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p]),
+    "arctopk_momentum_fold": (c_int32, [c_void_p, c_int32, POINTER(c_int64), POINTER(c_int64),
+                                        POINTER(c_void_p), c_double, c_double, c_int32, c_int32, c_void_p]),
     "arctopk_randk_select": (c_int32, [c_void_p, c_int32, POINTER(c_int64), POINTER(c_int64),
                                        POINTER(c_int64), POINTER(c_int64), c_uint64, c_void_p, c_void_p,
                                        c_void_p, c_int32, c_int32, c_void_p]),

@@ -9,12 +9,20 @@ switch by changing the import root from ``comm_hooks`` to
 """
 from __future__ import annotations
 
+import ctypes
 import logging
+import os
 
 import torch
 import torch.distributed as dist
 
+from allreducetopk_amd import _native as N
+
 logger = logging.getLogger(__name__)
+
+# (bucket dtype, moment dtype) pairs arctopk_momentum_fold is built for
+_MOMENTUM_PAIRS = {(torch.float32, torch.float32), (torch.bfloat16, torch.bfloat16),
+                   (torch.bfloat16, torch.float32)}
 
 
 def _get_allgather_out_list(all_gather_in_list, world_size):
@@ -44,6 +52,8 @@ class HookState:
         self.beta1 = None
         self.adam_freeze_key = False
         self.comm_bits_this_round = 0
+        self.momentum_native_calls = 0  # folds done by arctopk_momentum_fold (not the torch loop)
+        self._momentum_cache = {}       # bucket index -> (key, offsets, numels, moment pointers)
 
     def init_momentum_field(self, param_state, beta1):
         self.param_state = param_state
@@ -69,9 +79,69 @@ class HookState:
         parameters, gradients = bucket.parameters(), bucket.gradients()
         assert len(parameters) == len(gradients), \
             "The number of parameters and gradients should be the same."
-        for p, grad in zip(parameters, gradients):
-            st = self.param_state[p]
-            grad.mul_(1 - self.beta1).add_(st["exp_avg"], alpha=self.beta1)
+        moments = [self.param_state[p]["exp_avg"] for p in parameters]
+        if not self._accumulate_momentum_native(bucket, gradients, moments):
+            self._accumulate_momentum_torch(gradients, moments)
+
+    def _accumulate_momentum_torch(self, gradients, moments):
+        """The reference's loop: two torch ops per parameter (also the CPU path)."""
+        for grad, exp_avg in zip(gradients, moments):
+            grad.mul_(1 - self.beta1).add_(exp_avg, alpha=self.beta1)
+
+    def _momentum_fold_key(self, bucket, gradients, moments):
+        """What one native fold of ``bucket`` is made of -- (bucket dtype, moment dtype, view
+        offsets, numels, moment addresses) -- or None when the torch loop has to run: a CPU or
+        non-fp32/bf16 bucket, a gradient that is not a contiguous view into the buffer, a
+        moment that is not a contiguous tensor of the gradient's shape on the bucket's device,
+        or a (bucket, moment) dtype pair the library does not build."""
+        buf = bucket.buffer()
+        if not buf.is_cuda or not buf.is_contiguous() or buf.dtype not in N.DTYPE_CODE:
+            return None
+        storage, base, end = buf.untyped_storage().data_ptr(), buf.storage_offset(), buf.numel()
+        mom_dtype = moments[0].dtype if moments and isinstance(moments[0], torch.Tensor) else buf.dtype
+        if (buf.dtype, mom_dtype) not in _MOMENTUM_PAIRS:
+            return None
+        offsets, numels, ptrs = [], [], []
+        for grad, m in zip(gradients, moments):
+            off = grad.storage_offset() - base
+            if (grad.dtype != buf.dtype or grad.device != buf.device or not grad.is_contiguous()
+                    or grad.untyped_storage().data_ptr() != storage or off < 0
+                    or off + grad.numel() > end):
+                return None
+            if (not isinstance(m, torch.Tensor) or m.dtype != mom_dtype or m.device != buf.device
+                    or m.shape != grad.shape or not m.is_contiguous()):
+                return None
+            offsets.append(off)
+            numels.append(grad.numel())
+            ptrs.append(m.data_ptr())
+        return buf.dtype, mom_dtype, tuple(offsets), tuple(numels), tuple(ptrs)
+
+    def _accumulate_momentum_native(self, bucket, gradients, moments) -> bool:
+        """One arctopk_momentum_fold launch per bucket on the current stream; False when the
+        torch loop has to run instead (``ARCTOPK_MOMENTUM_NATIVE=0`` forces that)."""
+        if os.environ.get("ARCTOPK_MOMENTUM_NATIVE", "1") == "0":
+            return False
+        key = self._momentum_fold_key(bucket, gradients, moments)
+        if key is None:
+            return False
+        try:
+            L = N.lib()
+        except (ImportError, OSError):
+            return False
+        # the ctypes arrays of a bucket are kept until its views or moments change
+        # (optimizer.load_state_dict replaces the moments)
+        cached = self._momentum_cache.get(bucket.index())
+        if cached is None or cached[0] != key:
+            _, _, offsets, numels, ptrs = key
+            cached = (key, N.i64_array(offsets), N.i64_array(numels), (ctypes.c_void_p * len(ptrs))(*ptrs))
+            self._momentum_cache[bucket.index()] = cached
+        buf = bucket.buffer()
+        stream = torch.cuda.current_stream(buf.device).cuda_stream
+        N.check(L.arctopk_momentum_fold(buf.data_ptr(), len(key[2]), cached[1], cached[2], cached[3],
+                                        1 - self.beta1, self.beta1, N.DTYPE_CODE[key[0]],
+                                        N.DTYPE_CODE[key[1]], stream), "arctopk_momentum_fold")
+        self.momentum_native_calls += 1
+        return True
 
     def maybe_increase_iter(self, bucket):
         """Advance ``iter`` when the last bucket of a backward is processed (ref :67-75)."""

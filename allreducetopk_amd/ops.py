@@ -19,11 +19,15 @@ or any tensors of the sizes ``BucketPlan.info`` gives.
     dist.all_reduce(packed)
     torch.ops.arctopk.decode(h, packed, slotmap, ws, ef, gerr, grad)
 
+``torch.ops.arctopk.momentum_fold(bucket, moments, offsets, numels, 1 - beta1, beta1)`` is the
+momentum compression that precedes a hook call (HookState.accumulate_momentum_on_bucket).
+
 Each op replaces the same reference code as the C entry point it calls (include/arctopk.h).
 """
 from __future__ import annotations
 
-from typing import Optional
+import ctypes
+from typing import List, Optional
 
 import torch
 
@@ -77,6 +81,32 @@ def decode(plan: int, packed: torch.Tensor, slotmap: torch.Tensor, world_size: i
                                    _ptr(gerr), out.data_ptr(), _stream(out)), "arctopk_decode")
 
 
+@torch.library.custom_op("arctopk::momentum_fold", mutates_args=("bucket",))
+def momentum_fold(bucket: torch.Tensor, moments: List[torch.Tensor], offsets: List[int],
+                  numels: List[int], one_minus_beta: float, beta: float) -> None:
+    """bucket[offsets[i] : offsets[i] + numels[i]] := one_minus_beta * itself + beta * moments[i],
+    rounded as grad.mul_(one_minus_beta).add_(moment, alpha=beta) rounds on the GPU; one launch.
+    ``moments`` are contiguous, all of one dtype, each of numels[i] elements."""
+    if not (len(moments) == len(offsets) == len(numels)):
+        raise ValueError("momentum_fold: moments, offsets and numels must have the same length")
+    if any(not m.is_contiguous() or m.numel() != n or m.device != bucket.device
+           for m, n in zip(moments, numels)):
+        raise ValueError("momentum_fold: every moment must be contiguous, on the bucket's device "
+                         "and of numels[i] elements")
+    if not bucket.is_contiguous() or any(o < 0 or n < 0 or o + n > bucket.numel()
+                                         for o, n in zip(offsets, numels)):
+        raise ValueError("momentum_fold: a range lies outside the (contiguous) bucket")
+    mom_dtype = moments[0].dtype if moments else bucket.dtype
+    if bucket.dtype not in N.DTYPE_CODE or any(m.dtype != mom_dtype for m in moments) \
+            or mom_dtype not in N.DTYPE_CODE:
+        raise ValueError("momentum_fold: fp32 or bf16 bucket, moments of one fp32 or bf16 dtype")
+    ptrs = (ctypes.c_void_p * len(moments))(*[m.data_ptr() for m in moments])
+    N.check(N.lib().arctopk_momentum_fold(bucket.data_ptr(), len(moments), N.i64_array(offsets),
+                                          N.i64_array(numels), ptrs, one_minus_beta, beta,
+                                          N.DTYPE_CODE[bucket.dtype], N.DTYPE_CODE[mom_dtype],
+                                          _stream(bucket)), "arctopk_momentum_fold")
+
+
 # fake implementations: the ops only mutate their declared outputs
 @draw_projections.register_fake
 def _(plan, seed, V):
@@ -100,4 +130,9 @@ def _(plan, grad, err, ef, rowlist, slotmap, packed):
 
 @decode.register_fake
 def _(plan, packed, slotmap, world_size, ef, gerr, out):
+    return None
+
+
+@momentum_fold.register_fake
+def _(bucket, moments, offsets, numels, one_minus_beta, beta):
     return None

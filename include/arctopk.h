@@ -590,6 +590,29 @@ int arctopk_ef14_fold(const void* x, void* E, int64_t numel, int32_t err_in, int
                       void* stream);
 
 /*
+ * Momentum fold of a whole bucket, in place, stream-ordered, one launch per
+ * ARCTOPK_SPARSE_MAX_BATCH tensors: for every tensor i,
+ *   bucket[offsets[i] + j] = one_minus_beta * bucket[offsets[i] + j] + beta * moments[i][j],
+ * j < numels[i], rounded as the two torch ops round on the GPU: the product to the bucket's
+ * type, then one fused multiply-add of the moment rounded to it again; the scalars are the
+ * Python doubles (1 - beta1, beta1), cast to fp32 as torch casts them.
+ * offsets / numels / moments are host arrays of ntensors entries (element offsets into the
+ * bucket; moments[i] a device pointer to numels[i] contiguous elements of mom_dtype, any
+ * element-aligned address).  (dtype, mom_dtype) is (F32, F32), (BF16, BF16) or (BF16, F32);
+ * ARCTOPK_EDTYPE otherwise.  ARCTOPK_EINVAL for a null array or bucket, ntensors < 0, a
+ * negative offset or numel, a null moment with numel > 0, or a bucket / moment pointer not
+ * aligned to its element size; every check runs before any device call (host-testable).
+ * Tensors with numel 0 are skipped; ntensors == 0 enqueues nothing.  No allocation, no
+ * host-to-device copy, no synchronisation.
+ * Replaces: the per-parameter loop grad.mul_(1 - self.beta1).add_(exp_avg, alpha=self.beta1)
+ * of HookState.accumulate_momentum_on_bucket (comm_hooks/utils.py:54-65).
+ */
+int arctopk_momentum_fold(void* bucket, int32_t ntensors, const int64_t* offsets,
+                          const int64_t* numels, const void* const* moments,
+                          double one_minus_beta, double beta,
+                          int32_t dtype, int32_t mom_dtype, void* stream);
+
+/*
  * Device projections of one bucket call: for every SKETCH segment in bucket order,
  * V[v_off ..] = torch.randn(m, r, device=dev, dtype) as drawn by the reference on the GPU
  * right after torch.manual_seed(seed) (group_topk_hook_no_reshape.py:49, :79, :255):
