@@ -543,6 +543,34 @@ class GroupTopKState(HookState):
         # slot map, the pack or finalize and its stream (include/arctopk.h, arctopk_encode).
         self.err_zero_rows = os.environ.get("ARCTOPK_ERR_ZERO_ROWS", "1") != "0"
         self._zr: Dict[int, tuple] = {}
+        # EF14 residual dtype (not in the reference): None keeps the residual
+        # in the bucket's dtype; torch.float32 keeps a bf16 bucket's residual in fp32, so unsent
+        # mass below 2^-9 of a residual element is carried instead of rounded away (an fp32
+        # bucket's residual is fp32 already: the option then changes nothing).  The compressed call
+        # of such a bucket runs phase by phase (arctopk_encode_mixed / arctopk_pack_mixed), the
+        # Future complete on return.  Environment default: ARCTOPK_ERROR_DTYPE=fp32.
+        env = os.environ.get("ARCTOPK_ERROR_DTYPE", "")
+        if env not in ("", "fp32"):
+            raise ValueError(f"ARCTOPK_ERROR_DTYPE must be 'fp32' (or unset), got {env!r}")
+        self.error_dtype = torch.float32 if env == "fp32" else None
+        self.mixed_calls = 0  # compressed calls that ran with an fp32 residual under a bf16 bucket
+        self._mixed_buckets = set()  # ... and the buckets whose residual is such a one
+
+    def _mixed_residual(self, bucket_dtype, ef: int) -> bool:
+        """Whether this call keeps an fp32 EF14 residual under a bf16 bucket.  ValueError for an
+        ``error_dtype`` other than None / torch.float32, and for EF21 with it on a bf16 bucket (not
+        built: EF21's gE would need a decode of its own); ignored without error feedback."""
+        ed = self.error_dtype
+        if ed is None:
+            return False
+        if ed is not torch.float32:
+            raise ValueError(f"error_dtype must be None or torch.float32, got {ed!r}")
+        if bucket_dtype != torch.bfloat16 or ef == N.EF_NONE:
+            return False
+        if ef == N.EF21:
+            raise ValueError("error_dtype=torch.float32 is built for use_error_feedback='ef14' only: "
+                             "EF21 on a bfloat16 bucket keeps its residuals in bfloat16")
+        return True
 
     def residual_touched(self, b=None) -> None:
         """Tell the hook that bucket b's residual (None: every bucket's) was modified other than
@@ -663,12 +691,32 @@ class GroupTopKState(HookState):
 
     def state_dict(self) -> dict:
         self.flush_exchange()  # the deferred decode writes gE (EF21)
-        return super().state_dict()
+        out = super().state_dict()
+        # the residual dtype option, and the buckets whose fp32 residual belongs to a bf16 bucket
+        out["error_dtype"] = "fp32" if self.error_dtype is torch.float32 else None
+        out["mixed_buckets"] = sorted(self._mixed_buckets)
+        return out
 
     def load_state_dict(self, sd: dict, device=None) -> None:
+        """As HookState.load_state_dict.  A checkpoint written with ``error_dtype=torch.float32``
+        (fp32 residuals of bf16 buckets) loads only into a state that has the option set: ValueError
+        otherwise, since rounding those residuals to bf16 would drop what they exist to carry.  The
+        other way round -- bf16 EF14 residuals into a state with the option -- converts them to
+        fp32, which is exact."""
+        mixed = [int(b) for b in sd.get("mixed_buckets", ())]
+        if mixed and self.error_dtype is not torch.float32:
+            raise ValueError(f"the checkpoint holds float32 residuals of bfloat16 buckets {mixed} "
+                             "(error_dtype=torch.float32): set error_dtype=torch.float32 on this state "
+                             "before loading it")
         # a pending decode writes into the residuals being replaced (ADVICE r03)
         self.flush_exchange()
         super().load_state_dict(sd, device)
+        self._mixed_buckets = set(mixed)
+        if self.error_dtype is torch.float32 and self.use_error_feedback == "ef14":
+            for b, t in self.error_dict.items():
+                if t.dtype == torch.bfloat16:
+                    self.error_dict[b] = t.float()
+                    self._mixed_buckets.add(int(b))
 
     def _exchange_comms(self, group, dev):
         if self._comms is None:
@@ -1027,16 +1075,21 @@ def _check_bucket_layout(buf: torch.Tensor, grads) -> None:
 
 
 def _residual_on(table: Dict[int, torch.Tensor], b: int, bucket: torch.Tensor,
-                 name: str) -> torch.Tensor:
+                 name: str, dtype=None) -> torch.Tensor:
     """The residual of bucket b, checked before its pointer reaches a kernel: same numel and
     dtype as the bucket (else RuntimeError, as the reference's add_ raises), contiguous, on
     the bucket's device (a checkpoint loaded with map_location='cpu' or onto another rank's
-    device is moved there once and kept)."""
+    device is moved there once and kept).  `dtype`: the residual's dtype when it is not the
+    bucket's (torch.float32 under a bf16 bucket, GroupTopKState.error_dtype)."""
     t = table[b]
     if t.numel() != bucket.numel():
         raise RuntimeError(f"bucket {b} changed size ({t.numel()} -> {bucket.numel()}) after its "
                            f"residual ({name}) was created")
-    if t.dtype != bucket.dtype:
+    if dtype is not None and dtype != bucket.dtype:
+        if t.dtype != dtype:
+            raise RuntimeError(f"{name}[{b}] is {t.dtype} but error_dtype asks for {dtype} (set the "
+                               "option before the bucket's first compressed call, or load a checkpoint)")
+    elif t.dtype != bucket.dtype:
         raise RuntimeError(f"{name}[{b}] is {t.dtype} but the bucket is {bucket.dtype}")
     if t.device != bucket.device or not t.is_contiguous():
         t = t.to(bucket.device).contiguous()
@@ -1072,6 +1125,64 @@ def _stage_through_host(state: GroupTopKState, pv: torch.Tensor, stream, dev,
     stream.wait_stream(d2h)
 
 
+def _mixed_call(state: GroupTopKState, bucket, input_tensor: torch.Tensor, plan: BucketPlan,
+                err: torch.Tensor, err_in: bool, seed: int, group, world_size: int, sid: int
+                ) -> torch.futures.Future[torch.Tensor]:
+    """The compressed call of a bf16 bucket whose EF14 residual `err` is fp32 (error_dtype,
+    DESIGN.md section 4d): phase by phase on the caller's stream,
+
+        encode_mixed -> all-reduce(sketch) -> select -> pack_mixed -> all-reduce(packed) -> decode
+
+    with the collectives on the state's exchange communicators (none at world size 1 unless
+    force_exchange or an emulated wire asks for them).  Not used here: the one-call step, deferral,
+    exchange groups, select streams, trailing steps, keys mode, the riding pack and the fused
+    finalize; zero rows (err_in = 2) are never claimed, since a selected row of this residual keeps
+    its rounding remainder.  The Future is complete on return."""
+    dev = input_tensor.device
+    b = bucket.index()
+    L = _LIB[0]
+    if state._x_pend:  # deferred steps of other buckets: their decodes first, in order
+        _order_after_exchange(state, dev)
+    comms = world_size > 1 or state.force_exchange or state.emulate_wire is not None
+    sk = pk = None
+    if comms:
+        sk, pk = state._exchange_comms(group, dev)
+        if plan.comm_registered is not pk:
+            sk.register(plan.sketch)
+            pk.register(plan.packed)
+            plan.comm_registered = pk
+    vslot, V = -1, plan.V_ring[0]
+    if state.projections == "device":
+        if _claim_projections(state, plan, seed, sid, dev):
+            N.check(L.arctopk_draw_projections(plan.handle, seed, V.data_ptr(), sid), "arctopk_draw_projections")
+    else:
+        vslot, V = _host_projections(state, plan, bucket, seed, input_tensor.dtype, dev,
+                                     torch.cuda.current_stream(dev))
+    N.check(L.arctopk_encode_mixed(plan.handle, input_tensor.data_ptr(), err.data_ptr(), int(err_in),
+                                   V.data_ptr(), plan.sketch.data_ptr(), sid), "arctopk_encode_mixed")
+    if vslot >= 0:
+        plan.projection_consumed(vslot, torch.cuda.current_stream(dev))
+    if comms and plan.info.sketch_len:
+        sk.check(L.arctopk_comm_allreduce(sk.handle, plan.sketch.data_ptr(), int(plan.info.sketch_len),
+                                          N.BF16, sid), "arctopk_comm_allreduce(sketch)")
+    plan.select(world_size, sid)
+    N.check(L.arctopk_pack_mixed(plan.handle, input_tensor.data_ptr(), err.data_ptr(), int(err_in),
+                                 plan.rowlist.data_ptr(), plan.slotmap.data_ptr(), plan.packed.data_ptr(),
+                                 sid), "arctopk_pack_mixed")
+    if comms:
+        pk.check(L.arctopk_comm_allreduce(pk.handle, plan.packed.data_ptr(), int(plan.info.packed_len),
+                                          N.BF16, sid), "arctopk_comm_allreduce(packed)")
+    plan.decode(world_size, N.EF14, None, input_tensor, sid)
+    state._mixed_buckets.add(int(b))
+    state.mixed_calls += 1
+    state.comm_bits_this_round += 2 * (world_size - 1) * plan.bits_sum  # (:278)
+    state.maybe_increase_iter(bucket)
+    state._raise_if_comm_failed()
+    fut = torch.futures.Future()
+    fut.set_result(input_tensor)
+    return fut
+
+
 def group_topk_hook(state: GroupTopKState, bucket: dist.GradBucket
                     ) -> torch.futures.Future[torch.Tensor]:
     state.maybe_accumulate_momentum_on_bucket(bucket)
@@ -1094,11 +1205,13 @@ def group_topk_hook(state: GroupTopKState, bucket: dist.GradBucket
         raise ValueError(f"use_error_feedback must be noef/ef14/ef21, got {ef_name!r}")
     err = gerr = None
     err_in = True
+    # an fp32 EF14 residual under a bf16 bucket (state.error_dtype; raises for EF21 with it)
+    mixed = state._mixed_residual(input_tensor.dtype, ef)
     if ef == N.EF14:
         if b not in state.error_dict:
             logger.info("A zero tensor of length %s that represents local error is created.", total)
             state.error_dict[b] = torch.zeros(total, device=input_tensor.device,
-                                              dtype=input_tensor.dtype)
+                                              dtype=torch.float32 if mixed else input_tensor.dtype)
             err_in = False  # first call: the residual is not added (:228-230)
         err = state.error_dict[b]
     elif ef == N.EF21:
@@ -1118,7 +1231,8 @@ def group_topk_hook(state: GroupTopKState, bucket: dist.GradBucket
         err = state.error_dict[b]
         gerr = state.global_error_dict[b]
     if err is not None:
-        err = _residual_on(state.error_dict, b, input_tensor, "error_dict")
+        err = _residual_on(state.error_dict, b, input_tensor, "error_dict",
+                           torch.float32 if mixed else None)
         if gerr is not None:
             gerr = _residual_on(state.global_error_dict, b, input_tensor, "global_error_dict")
 
@@ -1140,6 +1254,8 @@ def group_topk_hook(state: GroupTopKState, bucket: dist.GradBucket
     L = _LIB[0]
     # EF14: may this call skip the rows its previous call zeroed?  (consumes the bucket's record)
     zr = state._zr_take(b, plan, err, ef)
+    if mixed:
+        return _mixed_call(state, bucket, input_tensor, plan, err, err_in, seed, group, world_size, sid)
     if not state.host_staged:
         # ONE native call per bucket (arctopk_exchange_step): the kernels, the collectives at
         # world size > 1 (or with force_exchange: the N > 1 code path over one-rank

@@ -39,6 +39,10 @@ row / per column of every tensor with the segmented select (arctopk_seg_select):
     EF14         arctopk_ef14_fold, then the select on E with the selected elements zeroed
 
 Ties at the k-th |x| resolve lowest-index first.
+
+Residuals are kept in the bucket's dtype: ``GroupTopKState.error_dtype`` (an fp32 EF14 residual
+under a bf16 bucket) belongs to the ARC-TopK hooks only; these hooks' bf16
+entry points round after every add, as the reference's torch ops do.
 """
 
 import logging

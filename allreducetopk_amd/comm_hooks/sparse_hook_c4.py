@@ -6,6 +6,9 @@ Differences from ``sparse_hook`` (reference sparse_hook_c4.py:140-151, :175-189,
 :224-237, :287): ``gradual_compression`` (default True) ramps the ratio from 0.8
 down to ``compress_ratio`` over ``start_compress_iter + warmup_iters`` iterations
 after compression starts, and ``cal_k`` takes ``(state, tensor)``.
+
+As in ``sparse_hook``, residuals stay in the bucket's dtype: the ARC-TopK hooks' ``error_dtype``
+option (fp32 EF14 residuals under a bf16 bucket) is not offered here.
 """
 
 import logging

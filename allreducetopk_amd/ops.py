@@ -22,6 +22,10 @@ or any tensors of the sizes ``BucketPlan.info`` gives.
 ``torch.ops.arctopk.momentum_fold(bucket, moments, offsets, numels, 1 - beta1, beta1)`` is the
 momentum compression that precedes a hook call (HookState.accumulate_momentum_on_bucket).
 
+``torch.ops.arctopk.encode_mixed`` / ``pack_mixed`` are the encode and pack of a bf16 bucket whose EF14
+residual is a float32 tensor (``GroupTopKState.error_dtype``); select and decode
+are the ops above.
+
 Each op replaces the same reference code as the C entry point it calls (include/arctopk.h).
 """
 from __future__ import annotations
@@ -107,6 +111,33 @@ def momentum_fold(bucket: torch.Tensor, moments: List[torch.Tensor], offsets: Li
                                           _stream(bucket)), "arctopk_momentum_fold")
 
 
+def _check_mixed(grad: Optional[torch.Tensor], err: torch.Tensor, what: str) -> None:
+    if err.dtype != torch.float32 or not err.is_contiguous():
+        raise ValueError(f"{what}: the residual must be a contiguous float32 tensor")
+    if grad is not None and (grad.dtype != torch.bfloat16 or grad.numel() != err.numel()
+                             or grad.device != err.device):
+        raise ValueError(f"{what}: a bfloat16 bucket of the residual's length, on its device")
+
+
+@torch.library.custom_op("arctopk::encode_mixed", mutates_args=("err", "sketch"))
+def encode_mixed(plan: int, grad: torch.Tensor, err: torch.Tensor, err_in: bool, V: torch.Tensor,
+                 sketch: torch.Tensor) -> None:
+    """EF14 pre-apply into an fp32 residual + the bf16 sketch of a bf16 bucket (arctopk_encode_mixed)."""
+    _check_mixed(grad, err, "encode_mixed")
+    N.check(N.lib().arctopk_encode_mixed(plan, grad.data_ptr(), err.data_ptr(), int(err_in), V.data_ptr(),
+                                         sketch.data_ptr(), _stream(grad)), "arctopk_encode_mixed")
+
+
+@torch.library.custom_op("arctopk::pack_mixed", mutates_args=("err", "packed"))
+def pack_mixed(plan: int, grad: Optional[torch.Tensor], err: torch.Tensor, err_in: bool,
+               rowlist: torch.Tensor, slotmap: torch.Tensor, packed: torch.Tensor) -> None:
+    """Selected rows -> bf16 packed values; the fp32 residual keeps X - packed (arctopk_pack_mixed)."""
+    _check_mixed(grad, err, "pack_mixed")
+    N.check(N.lib().arctopk_pack_mixed(plan, _ptr(grad), err.data_ptr(), int(err_in), rowlist.data_ptr(),
+                                       slotmap.data_ptr(), packed.data_ptr(), _stream(err)),
+            "arctopk_pack_mixed")
+
+
 # fake implementations: the ops only mutate their declared outputs
 @draw_projections.register_fake
 def _(plan, seed, V):
@@ -135,4 +166,14 @@ def _(plan, packed, slotmap, world_size, ef, gerr, out):
 
 @momentum_fold.register_fake
 def _(bucket, moments, offsets, numels, one_minus_beta, beta):
+    return None
+
+
+@encode_mixed.register_fake
+def _(plan, grad, err, err_in, V, sketch):
+    return None
+
+
+@pack_mixed.register_fake
+def _(plan, grad, err, err_in, rowlist, slotmap, packed):
     return None

@@ -613,6 +613,34 @@ int arctopk_momentum_fold(void* bucket, int32_t ntensors, const int64_t* offsets
                           int32_t dtype, int32_t mom_dtype, void* stream);
 
 /*
+ * EF14 with an fp32 residual under a bf16 bucket: the encode and pack
+ * phases of a bf16 plan whose residual `err_f32` holds plan.numel floats.  f = bf16 -> fp32
+ * (exact), b = fp32 -> bf16 as every bf16 value of the library is rounded (arctopk_round_bf16).
+ *   arctopk_encode_mixed : X = f(G) + E (err_in = 1) or f(G) (err_in = 0), one fp32 add; E := X;
+ *       sketch[SKETCH seg] = b(X.view(n, m) @ f(V)) (fp32 sums, one rounding), sketch[RAW seg] =
+ *       b(X); a DENSE segment has no encode work.  V and the sketch are the plan's bf16 layouts.
+ *   arctopk_pack_mixed   : every selected row (rowlist: arctopk_select's): packed = b(X), X read
+ *       from E; E := X - f(packed), one fp32 subtract (EF14's E = X - C[X]: the residual keeps the
+ *       rounding remainder of what was sent); other rows keep E = X.  A DENSE segment forms
+ *       X = f(G) + E (err_in, as given to the encode) here, every element selected; `grad` may be
+ *       NULL for a plan without DENSE segments.  The slot map is not written.
+ * Select and decode are arctopk_select and arctopk_decode(ef = ARCTOPK_EF14) on the same buffers.
+ * At world size 1 the decoded bucket satisfies f(out) + E_new == f(G) + E_old on every element.
+ * ARCTOPK_EINVAL for a plan that is not ARCTOPK_BF16, err_in outside {0, 1}, a null pointer the
+ * plan needs, or grad / err / packed not 16-B aligned.  Stream-ordered, no host synchronisation;
+ * the first of these calls on a plan builds its work tables (one allocation and copy, freed with
+ * the plan), every later one only enqueues.  err_in = 2 (zero rows) does not exist here: the
+ * selected rows of E are not zero.
+ * Replaces: input_tensor.add_(error) (:227), tensor @ V (:53, :83), the gathers (:70-71,
+ * :101-102) and EF14's tensor.view(-1)[indices] = 0 (:124) for a residual kept in fp32.
+ */
+int arctopk_encode_mixed(const arctopk_plan* plan, const void* grad_bf16, float* err_f32,
+                         int32_t err_in, const void* V_bf16, void* sketch_bf16, void* stream);
+int arctopk_pack_mixed(const arctopk_plan* plan, const void* grad_bf16, float* err_f32,
+                       int32_t err_in, const int32_t* rowlist, const int32_t* slotmap,
+                       void* packed_bf16, void* stream);
+
+/*
  * Device projections of one bucket call: for every SKETCH segment in bucket order,
  * V[v_off ..] = torch.randn(m, r, device=dev, dtype) as drawn by the reference on the GPU
  * right after torch.manual_seed(seed) (group_topk_hook_no_reshape.py:49, :79, :255):
