@@ -102,6 +102,9 @@ _SIGS = {
     "arctopk_encode_mixed": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "arctopk_pack_mixed": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
                                      c_void_p]),
+    "arctopk_encode_mixed21": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "arctopk_pack_mixed21": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "arctopk_decode_mixed21": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "arctopk_pack_segments": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32,
                                         c_void_p, c_void_p, c_void_p, c_void_p]),
     "arctopk_decode_segments": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32,

@@ -555,11 +555,23 @@ class GroupTopKState(HookState):
         self.error_dtype = torch.float32 if env == "fp32" else None
         self.mixed_calls = 0  # compressed calls that ran with an fp32 residual under a bf16 bucket
         self._mixed_buckets = set()  # ... and the buckets whose residual is such a one
+        # EF21 residual dtype (not in the reference): None keeps E and gE in the
+        # bucket's dtype; torch.float32 keeps both residuals of a bf16 bucket in fp32 (8 B per element
+        # for a 2-B bucket), so a mean below half a bf16 ulp of gE is added instead of dropped on every
+        # call.  An option of its own beside error_dtype, which stays EF14's; ignored for fp32
+        # buckets, noef and EF14.  The compressed call of such a bucket runs phase by phase
+        # (arctopk_encode_mixed21 / arctopk_pack_mixed21 / arctopk_decode_mixed21), the Future
+        # complete on return.  Environment default: ARCTOPK_EF21_ERROR_DTYPE=fp32.
+        env = os.environ.get("ARCTOPK_EF21_ERROR_DTYPE", "")
+        if env not in ("", "fp32"):
+            raise ValueError(f"ARCTOPK_EF21_ERROR_DTYPE must be 'fp32' (or unset), got {env!r}")
+        self.ef21_error_dtype = torch.float32 if env == "fp32" else None
 
     def _mixed_residual(self, bucket_dtype, ef: int) -> bool:
         """Whether this call keeps an fp32 EF14 residual under a bf16 bucket.  ValueError for an
-        ``error_dtype`` other than None / torch.float32, and for EF21 with it on a bf16 bucket (not
-        built: EF21's gE would need a decode of its own); ignored without error feedback."""
+        ``error_dtype`` other than None / torch.float32, and for EF21 with it on a bf16 bucket
+        unless ``ef21_error_dtype`` is set (EF21's fp32 residuals are that option's: two buffers, and
+        kernels of their own); ignored without error feedback."""
         ed = self.error_dtype
         if ed is None:
             return False
@@ -568,9 +580,23 @@ class GroupTopKState(HookState):
         if bucket_dtype != torch.bfloat16 or ef == N.EF_NONE:
             return False
         if ef == N.EF21:
+            if self.ef21_error_dtype is torch.float32:
+                return False  # (_mixed21_residual: that option's branch)
             raise ValueError("error_dtype=torch.float32 is built for use_error_feedback='ef14' only: "
-                             "EF21 on a bfloat16 bucket keeps its residuals in bfloat16")
+                             "EF21 on a bfloat16 bucket keeps its residuals in bfloat16 unless "
+                             "ef21_error_dtype=torch.float32 is set")
         return True
+
+    def _mixed21_residual(self, bucket_dtype, ef: int) -> bool:
+        """Whether this call keeps both EF21 residuals in fp32 under a bf16 bucket.  ValueError for an
+        ``ef21_error_dtype`` other than None / torch.float32; ignored for fp32 buckets, without
+        error feedback and for EF14."""
+        ed = self.ef21_error_dtype
+        if ed is None:
+            return False
+        if ed is not torch.float32:
+            raise ValueError(f"ef21_error_dtype must be None or torch.float32, got {ed!r}")
+        return bucket_dtype == torch.bfloat16 and ef == N.EF21
 
     def residual_touched(self, b=None) -> None:
         """Tell the hook that bucket b's residual (None: every bucket's) was modified other than
@@ -695,6 +721,7 @@ class GroupTopKState(HookState):
         # the residual dtype option, and the buckets whose fp32 residual belongs to a bf16 bucket
         out["error_dtype"] = "fp32" if self.error_dtype is torch.float32 else None
         out["mixed_buckets"] = sorted(self._mixed_buckets)
+        out["ef21_error_dtype"] = "fp32" if self.ef21_error_dtype is torch.float32 else None
         return out
 
     def load_state_dict(self, sd: dict, device=None) -> None:
@@ -702,12 +729,20 @@ class GroupTopKState(HookState):
         (fp32 residuals of bf16 buckets) loads only into a state that has the option set: ValueError
         otherwise, since rounding those residuals to bf16 would drop what they exist to carry.  The
         other way round -- bf16 EF14 residuals into a state with the option -- converts them to
-        fp32, which is exact."""
+        fp32, which is exact.  The same holds for ``ef21_error_dtype`` and the two EF21 residuals
+        (the buckets of ``mixed_buckets`` that have a global residual in the checkpoint)."""
         mixed = [int(b) for b in sd.get("mixed_buckets", ())]
-        if mixed and self.error_dtype is not torch.float32:
-            raise ValueError(f"the checkpoint holds float32 residuals of bfloat16 buckets {mixed} "
+        gkeys = {int(b) for b in sd.get("global_error_dict", {})}
+        mixed21 = [b for b in mixed if b in gkeys]
+        mixed14 = [b for b in mixed if b not in gkeys]
+        if mixed14 and self.error_dtype is not torch.float32:
+            raise ValueError(f"the checkpoint holds float32 residuals of bfloat16 buckets {mixed14} "
                              "(error_dtype=torch.float32): set error_dtype=torch.float32 on this state "
                              "before loading it")
+        if mixed21 and self.ef21_error_dtype is not torch.float32:
+            raise ValueError(f"the checkpoint holds float32 EF21 residuals of bfloat16 buckets {mixed21} "
+                             "(ef21_error_dtype=torch.float32): set ef21_error_dtype=torch.float32 on "
+                             "this state before loading it")
         # a pending decode writes into the residuals being replaced (ADVICE r03)
         self.flush_exchange()
         super().load_state_dict(sd, device)
@@ -717,6 +752,12 @@ class GroupTopKState(HookState):
                 if t.dtype == torch.bfloat16:
                     self.error_dict[b] = t.float()
                     self._mixed_buckets.add(int(b))
+        if self.ef21_error_dtype is torch.float32 and self.use_error_feedback == "ef21":
+            for table in (self.error_dict, self.global_error_dict):
+                for b, t in table.items():
+                    if t.dtype == torch.bfloat16:
+                        table[b] = t.float()
+                        self._mixed_buckets.add(int(b))
 
     def _exchange_comms(self, group, dev):
         if self._comms is None:
@@ -1075,19 +1116,20 @@ def _check_bucket_layout(buf: torch.Tensor, grads) -> None:
 
 
 def _residual_on(table: Dict[int, torch.Tensor], b: int, bucket: torch.Tensor,
-                 name: str, dtype=None) -> torch.Tensor:
+                 name: str, dtype=None, option: str = "error_dtype") -> torch.Tensor:
     """The residual of bucket b, checked before its pointer reaches a kernel: same numel and
     dtype as the bucket (else RuntimeError, as the reference's add_ raises), contiguous, on
     the bucket's device (a checkpoint loaded with map_location='cpu' or onto another rank's
     device is moved there once and kept).  `dtype`: the residual's dtype when it is not the
-    bucket's (torch.float32 under a bf16 bucket, GroupTopKState.error_dtype)."""
+    bucket's (torch.float32 under a bf16 bucket, GroupTopKState.error_dtype or, `option`,
+    ef21_error_dtype)."""
     t = table[b]
     if t.numel() != bucket.numel():
         raise RuntimeError(f"bucket {b} changed size ({t.numel()} -> {bucket.numel()}) after its "
                            f"residual ({name}) was created")
     if dtype is not None and dtype != bucket.dtype:
         if t.dtype != dtype:
-            raise RuntimeError(f"{name}[{b}] is {t.dtype} but error_dtype asks for {dtype} (set the "
+            raise RuntimeError(f"{name}[{b}] is {t.dtype} but {option} asks for {dtype} (set the "
                                "option before the bucket's first compressed call, or load a checkpoint)")
     elif t.dtype != bucket.dtype:
         raise RuntimeError(f"{name}[{b}] is {t.dtype} but the bucket is {bucket.dtype}")
@@ -1183,6 +1225,64 @@ def _mixed_call(state: GroupTopKState, bucket, input_tensor: torch.Tensor, plan:
     return fut
 
 
+def _mixed21_call(state: GroupTopKState, bucket, input_tensor: torch.Tensor, plan: BucketPlan,
+                  err: torch.Tensor, gerr: torch.Tensor, seed: int, group, world_size: int, sid: int
+                  ) -> torch.futures.Future[torch.Tensor]:
+    """The compressed call of a bf16 bucket whose EF21 residuals `err` (E) and `gerr` (gE) are both
+    fp32 (ef21_error_dtype): phase by phase on the caller's stream,
+
+        encode_mixed21 -> all-reduce(sketch) -> select -> pack_mixed21 -> all-reduce(packed)
+                       -> decode_mixed21
+
+    with the collectives on the state's exchange communicators, as _mixed_call runs them, and the
+    same parts of the hook unused (the one-call step, deferral, exchange groups, select streams,
+    trailing steps).  The encode only reads E; the pack adds what it sent to E; the decode adds the
+    fp32 mean to gE and writes b(gE) over the bucket.  The Future is complete on return."""
+    dev = input_tensor.device
+    b = bucket.index()
+    L = _LIB[0]
+    if state._x_pend:  # deferred steps of other buckets: their decodes first, in order
+        _order_after_exchange(state, dev)
+    comms = world_size > 1 or state.force_exchange or state.emulate_wire is not None
+    sk = pk = None
+    if comms:
+        sk, pk = state._exchange_comms(group, dev)
+        if plan.comm_registered is not pk:
+            sk.register(plan.sketch)
+            pk.register(plan.packed)
+            plan.comm_registered = pk
+    vslot, V = -1, plan.V_ring[0]
+    if state.projections == "device":
+        if _claim_projections(state, plan, seed, sid, dev):
+            N.check(L.arctopk_draw_projections(plan.handle, seed, V.data_ptr(), sid), "arctopk_draw_projections")
+    else:
+        vslot, V = _host_projections(state, plan, bucket, seed, input_tensor.dtype, dev,
+                                     torch.cuda.current_stream(dev))
+    N.check(L.arctopk_encode_mixed21(plan.handle, input_tensor.data_ptr(), err.data_ptr(), V.data_ptr(),
+                                     plan.sketch.data_ptr(), sid), "arctopk_encode_mixed21")
+    if vslot >= 0:
+        plan.projection_consumed(vslot, torch.cuda.current_stream(dev))
+    if comms and plan.info.sketch_len:
+        sk.check(L.arctopk_comm_allreduce(sk.handle, plan.sketch.data_ptr(), int(plan.info.sketch_len),
+                                          N.BF16, sid), "arctopk_comm_allreduce(sketch)")
+    plan.select(world_size, sid)
+    N.check(L.arctopk_pack_mixed21(plan.handle, input_tensor.data_ptr(), err.data_ptr(), plan.rowlist.data_ptr(),
+                                   plan.slotmap.data_ptr(), plan.packed.data_ptr(), sid), "arctopk_pack_mixed21")
+    if comms:
+        pk.check(L.arctopk_comm_allreduce(pk.handle, plan.packed.data_ptr(), int(plan.info.packed_len),
+                                          N.BF16, sid), "arctopk_comm_allreduce(packed)")
+    N.check(L.arctopk_decode_mixed21(plan.handle, plan.packed.data_ptr(), plan.slotmap.data_ptr(), world_size,
+                                     gerr.data_ptr(), input_tensor.data_ptr(), sid), "arctopk_decode_mixed21")
+    state._mixed_buckets.add(int(b))
+    state.mixed_calls += 1
+    state.comm_bits_this_round += 2 * (world_size - 1) * plan.bits_sum  # (:278)
+    state.maybe_increase_iter(bucket)
+    state._raise_if_comm_failed()
+    fut = torch.futures.Future()
+    fut.set_result(input_tensor)
+    return fut
+
+
 def group_topk_hook(state: GroupTopKState, bucket: dist.GradBucket
                     ) -> torch.futures.Future[torch.Tensor]:
     state.maybe_accumulate_momentum_on_bucket(bucket)
@@ -1205,7 +1305,9 @@ def group_topk_hook(state: GroupTopKState, bucket: dist.GradBucket
         raise ValueError(f"use_error_feedback must be noef/ef14/ef21, got {ef_name!r}")
     err = gerr = None
     err_in = True
-    # an fp32 EF14 residual under a bf16 bucket (state.error_dtype; raises for EF21 with it)
+    # an fp32 EF14 residual under a bf16 bucket (state.error_dtype; raises for EF21 with it alone),
+    # or both EF21 residuals in fp32 under one (state.ef21_error_dtype)
+    mixed21 = state._mixed21_residual(input_tensor.dtype, ef)
     mixed = state._mixed_residual(input_tensor.dtype, ef)
     if ef == N.EF14:
         if b not in state.error_dict:
@@ -1217,13 +1319,15 @@ def group_topk_hook(state: GroupTopKState, bucket: dist.GradBucket
     elif ef == N.EF21:
         if b not in state.error_dict:  # E_0 = grad; all-reduce grad; gE_0 = mean (:236-250)
             logger.info("A tensor of length %s that represents local/global error is created.", total)
-            state.error_dict[b] = torch.clone(input_tensor).detach()
+            state.error_dict[b] = input_tensor.float() if mixed21 else torch.clone(input_tensor).detach()
             state.comm_bits_this_round += tensor_bits(input_tensor)
             if state._x_pend:
                 _order_after_exchange(state, input_tensor.device)
             dist.all_reduce(input_tensor, group=group, async_op=False)
             input_tensor.div_(world_size)
-            state.global_error_dict[b] = torch.clone(input_tensor).detach()
+            state.global_error_dict[b] = input_tensor.float() if mixed21 else torch.clone(input_tensor).detach()
+            if mixed21:
+                state._mixed_buckets.add(int(b))
             state.maybe_increase_iter(bucket)
             fut = torch.futures.Future()
             fut.set_result(input_tensor)
@@ -1232,9 +1336,11 @@ def group_topk_hook(state: GroupTopKState, bucket: dist.GradBucket
         gerr = state.global_error_dict[b]
     if err is not None:
         err = _residual_on(state.error_dict, b, input_tensor, "error_dict",
-                           torch.float32 if mixed else None)
+                           torch.float32 if (mixed or mixed21) else None,
+                           "ef21_error_dtype" if mixed21 else "error_dtype")
         if gerr is not None:
-            gerr = _residual_on(state.global_error_dict, b, input_tensor, "global_error_dict")
+            gerr = _residual_on(state.global_error_dict, b, input_tensor, "global_error_dict",
+                                torch.float32 if mixed21 else None, "ef21_error_dtype")
 
     # per-call projection seed, and the reference's global reseed side effect (:254-255)
     _ht()
@@ -1256,6 +1362,8 @@ def group_topk_hook(state: GroupTopKState, bucket: dist.GradBucket
     zr = state._zr_take(b, plan, err, ef)
     if mixed:
         return _mixed_call(state, bucket, input_tensor, plan, err, err_in, seed, group, world_size, sid)
+    if mixed21:
+        return _mixed21_call(state, bucket, input_tensor, plan, err, gerr, seed, group, world_size, sid)
     if not state.host_staged:
         # ONE native call per bucket (arctopk_exchange_step): the kernels, the collectives at
         # world size > 1 (or with force_exchange: the N > 1 code path over one-rank

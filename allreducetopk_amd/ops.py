@@ -26,6 +26,10 @@ momentum compression that precedes a hook call (HookState.accumulate_momentum_on
 residual is a float32 tensor (``GroupTopKState.error_dtype``); select and decode
 are the ops above.
 
+``torch.ops.arctopk.encode_mixed21`` / ``pack_mixed21`` / ``decode_mixed21`` are the three phases of a
+bf16 bucket whose EF21 residuals are both float32 tensors (``GroupTopKState.ef21_error_dtype``, DESIGN.md
+section 4e); the select between them is the op above.
+
 Each op replaces the same reference code as the C entry point it calls (include/arctopk.h).
 """
 from __future__ import annotations
@@ -138,6 +142,36 @@ def pack_mixed(plan: int, grad: Optional[torch.Tensor], err: torch.Tensor, err_i
             "arctopk_pack_mixed")
 
 
+@torch.library.custom_op("arctopk::encode_mixed21", mutates_args=("sketch",))
+def encode_mixed21(plan: int, grad: torch.Tensor, err: torch.Tensor, V: torch.Tensor, sketch: torch.Tensor) -> None:
+    """The bf16 sketch of D = float(G) - E for an fp32 EF21 residual E, which is only read
+    (arctopk_encode_mixed21)."""
+    _check_mixed(grad, err, "encode_mixed21")
+    N.check(N.lib().arctopk_encode_mixed21(plan, grad.data_ptr(), err.data_ptr(), V.data_ptr(),
+                                           sketch.data_ptr(), _stream(grad)), "arctopk_encode_mixed21")
+
+
+@torch.library.custom_op("arctopk::pack_mixed21", mutates_args=("err", "packed"))
+def pack_mixed21(plan: int, grad: torch.Tensor, err: torch.Tensor, rowlist: torch.Tensor, slotmap: torch.Tensor,
+                 packed: torch.Tensor) -> None:
+    """Selected rows -> packed = bf16(D); the fp32 residual E += float(packed) (arctopk_pack_mixed21)."""
+    _check_mixed(grad, err, "pack_mixed21")
+    N.check(N.lib().arctopk_pack_mixed21(plan, grad.data_ptr(), err.data_ptr(), rowlist.data_ptr(),
+                                         slotmap.data_ptr(), packed.data_ptr(), _stream(grad)),
+            "arctopk_pack_mixed21")
+
+
+@torch.library.custom_op("arctopk::decode_mixed21", mutates_args=("gerr", "out"))
+def decode_mixed21(plan: int, packed: torch.Tensor, slotmap: torch.Tensor, world_size: int, gerr: torch.Tensor,
+                   out: torch.Tensor) -> None:
+    """Selected elements: gE += float(packed) / world_size in fp32; out = bf16(gE) everywhere
+    (arctopk_decode_mixed21)."""
+    _check_mixed(out, gerr, "decode_mixed21")
+    N.check(N.lib().arctopk_decode_mixed21(plan, packed.data_ptr(), slotmap.data_ptr(), world_size,
+                                           gerr.data_ptr(), out.data_ptr(), _stream(out)),
+            "arctopk_decode_mixed21")
+
+
 # fake implementations: the ops only mutate their declared outputs
 @draw_projections.register_fake
 def _(plan, seed, V):
@@ -176,4 +210,19 @@ def _(plan, grad, err, err_in, V, sketch):
 
 @pack_mixed.register_fake
 def _(plan, grad, err, err_in, rowlist, slotmap, packed):
+    return None
+
+
+@encode_mixed21.register_fake
+def _(plan, grad, err, V, sketch):
+    return None
+
+
+@pack_mixed21.register_fake
+def _(plan, grad, err, rowlist, slotmap, packed):
+    return None
+
+
+@decode_mixed21.register_fake
+def _(plan, packed, slotmap, world_size, gerr, out):
     return None

@@ -641,6 +641,40 @@ int arctopk_pack_mixed(const arctopk_plan* plan, const void* grad_bf16, float* e
                        void* packed_bf16, void* stream);
 
 /*
+ * EF21 with both residuals in fp32 under a bf16 bucket: the encode, pack
+ * and decode phases of a bf16 plan whose local residual `err_f32` (E) and global residual
+ * `gerr_f32` (gE) hold plan.numel floats each.  f and b as above.
+ *   arctopk_encode_mixed21 : D = f(G) - E, one fp32 subtract; sketch[SKETCH seg] =
+ *       b(D.view(n, m) @ f(V)) (fp32 sums, one rounding), sketch[RAW seg] = b(D); a DENSE segment
+ *       has no encode work.  Nothing but the sketch is written: E is read only.
+ *   arctopk_pack_mixed21   : every selected row (rowlist: arctopk_select's; every entry is checked
+ *       against the segment's rows) and every element of a DENSE segment: D as above, packed =
+ *       b(D), E := E + f(packed), one fp32 add (EF21's E += C[G - E] with C what was sent: the
+ *       rounding remainder D - f(packed) stays in G - E).  Other rows are not touched.  The slot
+ *       map is not written.
+ *   arctopk_decode_mixed21 : `packed` holds the all-reduced values.  A selected element (slot map:
+ *       arctopk_select's; every element of a DENSE segment): gE := gE + f(P) / world_size, the
+ *       correctly rounded fp32 quotient, not rounded to bf16 before the add.  out = b(gE) on every
+ *       element of the bucket; gE of unselected rows is read and left as stored.  `out` may be the
+ *       bucket itself.
+ * Select is arctopk_select on the same buffers.  At world size 1, gE == E bit for bit after every
+ * call of a bucket whose first call set E = f(G), gE = f(out).
+ * ARCTOPK_EINVAL for a plan that is not ARCTOPK_BF16, a null pointer, world_size < 1, or grad /
+ * err / gerr / packed / out not 16-B aligned.  Stream-ordered, no host synchronisation; work tables
+ * as for arctopk_encode_mixed (the same ones, with the decode's tiles).
+ * Replaces: input_tensor.add_(error, alpha=-1.0) (:234), tensor @ V (:53, :83), the gathers
+ * (:70-71, :101-102), EF21's error.add_(input_tensor) (:275) and global_error.add_(input_tensor);
+ * input_tensor.copy_(global_error) (:289-290) for residuals kept in fp32.
+ */
+int arctopk_encode_mixed21(const arctopk_plan* plan, const void* grad_bf16, const float* err_f32,
+                           const void* V_bf16, void* sketch_bf16, void* stream);
+int arctopk_pack_mixed21(const arctopk_plan* plan, const void* grad_bf16, float* err_f32,
+                         const int32_t* rowlist, const int32_t* slotmap, void* packed_bf16,
+                         void* stream);
+int arctopk_decode_mixed21(const arctopk_plan* plan, const void* packed_bf16, const int32_t* slotmap,
+                           int32_t world_size, float* gerr_f32, void* out_bf16, void* stream);
+
+/*
  * Device projections of one bucket call: for every SKETCH segment in bucket order,
  * V[v_off ..] = torch.randn(m, r, device=dev, dtype) as drawn by the reference on the GPU
  * right after torch.manual_seed(seed) (group_topk_hook_no_reshape.py:49, :79, :255):
