@@ -38,7 +38,7 @@ import logging
 import os
 import time
 import weakref
-from typing import Dict, List, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import torch
 import torch.distributed as dist
@@ -567,16 +567,21 @@ class GroupTopKState(HookState):
             raise ValueError(f"ARCTOPK_EF21_ERROR_DTYPE must be 'fp32' (or unset), got {env!r}")
         self.ef21_error_dtype = torch.float32 if env == "fp32" else None
 
+    def _fp32_residual_option(self, name: str) -> bool:
+        """Whether the residual-dtype option `name` is torch.float32; ValueError unless it is that
+        or None."""
+        ed = getattr(self, name)
+        if ed is not None and ed is not torch.float32:
+            raise ValueError(f"{name} must be None or torch.float32, got {ed!r}")
+        return ed is not None
+
     def _mixed_residual(self, bucket_dtype, ef: int) -> bool:
         """Whether this call keeps an fp32 EF14 residual under a bf16 bucket.  ValueError for an
         ``error_dtype`` other than None / torch.float32, and for EF21 with it on a bf16 bucket
-        unless ``ef21_error_dtype`` is set (EF21's fp32 residuals are that option's: two buffers, and
-        kernels of their own); ignored without error feedback."""
-        ed = self.error_dtype
-        if ed is None:
+        unless ``ef21_error_dtype`` is set (EF21's fp32 residuals are that option's: two buffers and
+        a residual rule of their own); ignored without error feedback."""
+        if not self._fp32_residual_option("error_dtype"):
             return False
-        if ed is not torch.float32:
-            raise ValueError(f"error_dtype must be None or torch.float32, got {ed!r}")
         if bucket_dtype != torch.bfloat16 or ef == N.EF_NONE:
             return False
         if ef == N.EF21:
@@ -591,12 +596,8 @@ class GroupTopKState(HookState):
         """Whether this call keeps both EF21 residuals in fp32 under a bf16 bucket.  ValueError for an
         ``ef21_error_dtype`` other than None / torch.float32; ignored for fp32 buckets, without
         error feedback and for EF14."""
-        ed = self.ef21_error_dtype
-        if ed is None:
-            return False
-        if ed is not torch.float32:
-            raise ValueError(f"ef21_error_dtype must be None or torch.float32, got {ed!r}")
-        return bucket_dtype == torch.bfloat16 and ef == N.EF21
+        return (self._fp32_residual_option("ef21_error_dtype")
+                and bucket_dtype == torch.bfloat16 and ef == N.EF21)
 
     def residual_touched(self, b=None) -> None:
         """Tell the hook that bucket b's residual (None: every bucket's) was modified other than
@@ -1167,22 +1168,26 @@ def _stage_through_host(state: GroupTopKState, pv: torch.Tensor, stream, dev,
     stream.wait_stream(d2h)
 
 
-def _mixed_call(state: GroupTopKState, bucket, input_tensor: torch.Tensor, plan: BucketPlan,
-                err: torch.Tensor, err_in: bool, seed: int, group, world_size: int, sid: int
-                ) -> torch.futures.Future[torch.Tensor]:
-    """The compressed call of a bf16 bucket whose EF14 residual `err` is fp32 (error_dtype,
-    DESIGN.md section 4d): phase by phase on the caller's stream,
+def _mixed_call(state: GroupTopKState, bucket, input_tensor: torch.Tensor, plan: BucketPlan, ef: int,
+                err: torch.Tensor, gerr: Optional[torch.Tensor], err_in: bool, seed: int, group,
+                world_size: int, sid: int) -> torch.futures.Future[torch.Tensor]:
+    """The compressed call of a bf16 bucket whose residuals are fp32: EF14's `err` (error_dtype,
+    DESIGN.md section 4d; `gerr` is None) or EF21's `err` (E) and `gerr` (gE) (ef21_error_dtype,
+    section 4e).  Phase by phase on the caller's stream,
 
-        encode_mixed -> all-reduce(sketch) -> select -> pack_mixed -> all-reduce(packed) -> decode
+        EF14: encode_mixed   -> all-reduce(sketch) -> select -> pack_mixed   -> all-reduce(packed) -> decode
+        EF21: encode_mixed21 -> all-reduce(sketch) -> select -> pack_mixed21 -> all-reduce(packed) -> decode_mixed21
 
     with the collectives on the state's exchange communicators (none at world size 1 unless
-    force_exchange or an emulated wire asks for them).  Not used here: the one-call step, deferral,
-    exchange groups, select streams, trailing steps, keys mode, the riding pack and the fused
-    finalize; zero rows (err_in = 2) are never claimed, since a selected row of this residual keeps
-    its rounding remainder.  The Future is complete on return."""
+    force_exchange or an emulated wire asks for them).  EF21's encode only reads E; its pack adds
+    what it sent to E; its decode adds the fp32 mean to gE and writes b(gE) over the bucket.  Not
+    used here: the one-call step, deferral, exchange groups, select streams, trailing steps, keys
+    mode, the riding pack and the fused finalize; zero rows (err_in = 2) are never claimed, since a
+    selected row of EF14's residual keeps its rounding remainder.  The Future is complete on return."""
     dev = input_tensor.device
     b = bucket.index()
     L = _LIB[0]
+    ef21 = ef == N.EF21
     if state._x_pend:  # deferred steps of other buckets: their decodes first, in order
         _order_after_exchange(state, dev)
     comms = world_size > 1 or state.force_exchange or state.emulate_wire is not None
@@ -1200,79 +1205,34 @@ def _mixed_call(state: GroupTopKState, bucket, input_tensor: torch.Tensor, plan:
     else:
         vslot, V = _host_projections(state, plan, bucket, seed, input_tensor.dtype, dev,
                                      torch.cuda.current_stream(dev))
-    N.check(L.arctopk_encode_mixed(plan.handle, input_tensor.data_ptr(), err.data_ptr(), int(err_in),
-                                   V.data_ptr(), plan.sketch.data_ptr(), sid), "arctopk_encode_mixed")
-    if vslot >= 0:
-        plan.projection_consumed(vslot, torch.cuda.current_stream(dev))
-    if comms and plan.info.sketch_len:
-        sk.check(L.arctopk_comm_allreduce(sk.handle, plan.sketch.data_ptr(), int(plan.info.sketch_len),
-                                          N.BF16, sid), "arctopk_comm_allreduce(sketch)")
-    plan.select(world_size, sid)
-    N.check(L.arctopk_pack_mixed(plan.handle, input_tensor.data_ptr(), err.data_ptr(), int(err_in),
-                                 plan.rowlist.data_ptr(), plan.slotmap.data_ptr(), plan.packed.data_ptr(),
-                                 sid), "arctopk_pack_mixed")
-    if comms:
-        pk.check(L.arctopk_comm_allreduce(pk.handle, plan.packed.data_ptr(), int(plan.info.packed_len),
-                                          N.BF16, sid), "arctopk_comm_allreduce(packed)")
-    plan.decode(world_size, N.EF14, None, input_tensor, sid)
-    state._mixed_buckets.add(int(b))
-    state.mixed_calls += 1
-    state.comm_bits_this_round += 2 * (world_size - 1) * plan.bits_sum  # (:278)
-    state.maybe_increase_iter(bucket)
-    state._raise_if_comm_failed()
-    fut = torch.futures.Future()
-    fut.set_result(input_tensor)
-    return fut
-
-
-def _mixed21_call(state: GroupTopKState, bucket, input_tensor: torch.Tensor, plan: BucketPlan,
-                  err: torch.Tensor, gerr: torch.Tensor, seed: int, group, world_size: int, sid: int
-                  ) -> torch.futures.Future[torch.Tensor]:
-    """The compressed call of a bf16 bucket whose EF21 residuals `err` (E) and `gerr` (gE) are both
-    fp32 (ef21_error_dtype): phase by phase on the caller's stream,
-
-        encode_mixed21 -> all-reduce(sketch) -> select -> pack_mixed21 -> all-reduce(packed)
-                       -> decode_mixed21
-
-    with the collectives on the state's exchange communicators, as _mixed_call runs them, and the
-    same parts of the hook unused (the one-call step, deferral, exchange groups, select streams,
-    trailing steps).  The encode only reads E; the pack adds what it sent to E; the decode adds the
-    fp32 mean to gE and writes b(gE) over the bucket.  The Future is complete on return."""
-    dev = input_tensor.device
-    b = bucket.index()
-    L = _LIB[0]
-    if state._x_pend:  # deferred steps of other buckets: their decodes first, in order
-        _order_after_exchange(state, dev)
-    comms = world_size > 1 or state.force_exchange or state.emulate_wire is not None
-    sk = pk = None
-    if comms:
-        sk, pk = state._exchange_comms(group, dev)
-        if plan.comm_registered is not pk:
-            sk.register(plan.sketch)
-            pk.register(plan.packed)
-            plan.comm_registered = pk
-    vslot, V = -1, plan.V_ring[0]
-    if state.projections == "device":
-        if _claim_projections(state, plan, seed, sid, dev):
-            N.check(L.arctopk_draw_projections(plan.handle, seed, V.data_ptr(), sid), "arctopk_draw_projections")
+    if ef21:
+        N.check(L.arctopk_encode_mixed21(plan.handle, input_tensor.data_ptr(), err.data_ptr(), V.data_ptr(),
+                                         plan.sketch.data_ptr(), sid), "arctopk_encode_mixed21")
     else:
-        vslot, V = _host_projections(state, plan, bucket, seed, input_tensor.dtype, dev,
-                                     torch.cuda.current_stream(dev))
-    N.check(L.arctopk_encode_mixed21(plan.handle, input_tensor.data_ptr(), err.data_ptr(), V.data_ptr(),
-                                     plan.sketch.data_ptr(), sid), "arctopk_encode_mixed21")
+        N.check(L.arctopk_encode_mixed(plan.handle, input_tensor.data_ptr(), err.data_ptr(), int(err_in),
+                                       V.data_ptr(), plan.sketch.data_ptr(), sid), "arctopk_encode_mixed")
     if vslot >= 0:
         plan.projection_consumed(vslot, torch.cuda.current_stream(dev))
     if comms and plan.info.sketch_len:
         sk.check(L.arctopk_comm_allreduce(sk.handle, plan.sketch.data_ptr(), int(plan.info.sketch_len),
                                           N.BF16, sid), "arctopk_comm_allreduce(sketch)")
     plan.select(world_size, sid)
-    N.check(L.arctopk_pack_mixed21(plan.handle, input_tensor.data_ptr(), err.data_ptr(), plan.rowlist.data_ptr(),
-                                   plan.slotmap.data_ptr(), plan.packed.data_ptr(), sid), "arctopk_pack_mixed21")
+    if ef21:
+        N.check(L.arctopk_pack_mixed21(plan.handle, input_tensor.data_ptr(), err.data_ptr(),
+                                       plan.rowlist.data_ptr(), plan.slotmap.data_ptr(), plan.packed.data_ptr(),
+                                       sid), "arctopk_pack_mixed21")
+    else:
+        N.check(L.arctopk_pack_mixed(plan.handle, input_tensor.data_ptr(), err.data_ptr(), int(err_in),
+                                     plan.rowlist.data_ptr(), plan.slotmap.data_ptr(), plan.packed.data_ptr(),
+                                     sid), "arctopk_pack_mixed")
     if comms:
         pk.check(L.arctopk_comm_allreduce(pk.handle, plan.packed.data_ptr(), int(plan.info.packed_len),
                                           N.BF16, sid), "arctopk_comm_allreduce(packed)")
-    N.check(L.arctopk_decode_mixed21(plan.handle, plan.packed.data_ptr(), plan.slotmap.data_ptr(), world_size,
-                                     gerr.data_ptr(), input_tensor.data_ptr(), sid), "arctopk_decode_mixed21")
+    if ef21:
+        N.check(L.arctopk_decode_mixed21(plan.handle, plan.packed.data_ptr(), plan.slotmap.data_ptr(), world_size,
+                                         gerr.data_ptr(), input_tensor.data_ptr(), sid), "arctopk_decode_mixed21")
+    else:
+        plan.decode(world_size, N.EF14, None, input_tensor, sid)
     state._mixed_buckets.add(int(b))
     state.mixed_calls += 1
     state.comm_bits_this_round += 2 * (world_size - 1) * plan.bits_sum  # (:278)
@@ -1360,10 +1320,8 @@ def group_topk_hook(state: GroupTopKState, bucket: dist.GradBucket
     L = _LIB[0]
     # EF14: may this call skip the rows its previous call zeroed?  (consumes the bucket's record)
     zr = state._zr_take(b, plan, err, ef)
-    if mixed:
-        return _mixed_call(state, bucket, input_tensor, plan, err, err_in, seed, group, world_size, sid)
-    if mixed21:
-        return _mixed21_call(state, bucket, input_tensor, plan, err, gerr, seed, group, world_size, sid)
+    if mixed or mixed21:
+        return _mixed_call(state, bucket, input_tensor, plan, ef, err, gerr, err_in, seed, group, world_size, sid)
     if not state.host_staged:
         # ONE native call per bucket (arctopk_exchange_step): the kernels, the collectives at
         # world size > 1 (or with force_exchange: the N > 1 code path over one-rank

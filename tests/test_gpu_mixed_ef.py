@@ -208,6 +208,42 @@ def test_pack_phase(name, err_in):
     assert torch.equal(out.float().cpu() + Ed.cpu(), X), "f(out) + E_new == f(G) + E_old"
 
 
+@pytest.mark.parametrize("err_in", [0, 1])
+@pytest.mark.parametrize("name", ["mix10", "aligned"])
+def test_pack_without_grad(name, err_in):
+    """arctopk_pack_mixed takes grad = NULL for a plan without DENSE segments (a selected row's X is
+    the E the encode stored: G is not read): packed values and E bit-exact as in test_pack_phase."""
+    shapes = ALIGNED if name == "aligned" else MIX10
+    G, E0, g = _inputs(shapes, 23)
+    plan = BucketPlan([tuple(s) for s in shapes], 4, 0.25, BF16, DEV)
+    V = torch.randn(plan.info.v_len, generator=g).to(BF16)
+    buf, Ed = _guarded(E0 if err_in else torch.zeros_like(E0))
+    _encode(plan, G.to(DEV), Ed, err_in, V.to(DEV))
+    plan.select(1, _stream())
+    st = N.lib().arctopk_pack_mixed(plan.handle, None, Ed.data_ptr(), err_in, plan.rowlist.data_ptr(),
+                                    plan.slotmap.data_ptr(), plan.packed.data_ptr(), _stream())
+    assert st == 0
+    torch.cuda.synchronize()
+    assert _guards_intact(buf), "a write outside the residual"
+    segs = MX.segments(shapes, 0.25)
+    X, _ = MX.encode(G, E0 if err_in else None, segs, _plan_Vs(plan, V))
+    vals, E_new = MX.pack(X, _rows(plan), segs)
+    assert_bitwise(plan.packed_values(), vals, f"{name} err_in {err_in}, grad = NULL: packed = b(X)")
+    assert_bitwise(Ed, E_new, f"{name} err_in {err_in}, grad = NULL: E = X - f(packed) on the rows, X elsewhere")
+
+
+@pytest.mark.parametrize("err_in", [0, 1])
+def test_pack_without_grad_refused_with_dense_segments(err_in):
+    """A DENSE segment's X = f(G) + E is formed by the pack: grad = NULL is EINVAL (a host check)."""
+    plan = BucketPlan([tuple(s) for s in MIX10], 4, 0.25, BF16, DEV, flags=N.PLAN_DENSE_1D)
+    Ed = torch.zeros(plan.info.numel, device=DEV)
+    st = N.lib().arctopk_pack_mixed(plan.handle, None, Ed.data_ptr(), err_in, plan.rowlist.data_ptr(),
+                                    plan.slotmap.data_ptr(), plan.packed.data_ptr(), _stream())
+    assert st == N.EINVAL
+    torch.cuda.synchronize()
+    assert not Ed.any() and not plan.packed.any(), "nothing was launched"
+
+
 # ---- 3. the hook -------------------------------------------------------------------------
 def _hook_state(c4, seed, **kw):
     if c4:  # two ramp calls (restarted draws, ratios 0.8 and 0.525), then steady ones
