@@ -177,6 +177,10 @@ class BucketPlan:
         self.v_drawn = None
         self.v_stream = None
         self.comm_registered = None  # the exchange communicator this plan's buffers are known to
+        # the packed values as bf16 (GroupTopKState.wire_dtype): allocated by the plan's first call
+        # on that branch, and the packed communicator it is registered with
+        self.packed16 = None
+        self.packed16_registered = None
         # the device generator's Philox offset after the reference's per-tensor
         # torch.randn(m, r, device=...) draws of one call (see _reseed_global)
         adv = N.c_uint64()
@@ -566,6 +570,35 @@ class GroupTopKState(HookState):
         if env not in ("", "fp32"):
             raise ValueError(f"ARCTOPK_EF21_ERROR_DTYPE must be 'fp32' (or unset), got {env!r}")
         self.ef21_error_dtype = torch.float32 if env == "fp32" else None
+        # Wire dtype of the packed values (not in the reference): None sends them
+        # in the bucket's dtype; torch.bfloat16 sends an fp32 bucket's packed values as bf16 (half
+        # the bytes of the packed all-reduce; the sketch stays fp32, so the selection is the default
+        # path's).  With EF14 / EF21 the residual keeps the rounding remainder of what was sent
+        # (X - f(b(X)) is exact in fp32); with noef it is lost.  Ignored for bf16 buckets, whose wire
+        # is bf16 already.  The compressed call of such a bucket runs phase by phase
+        # (arctopk_encode / arctopk_pack_wire16 / arctopk_decode_wire16), the Future complete on
+        # return.  Environment default: ARCTOPK_WIRE_DTYPE=bf16.
+        env = os.environ.get("ARCTOPK_WIRE_DTYPE", "")
+        if env not in ("", "bf16"):
+            raise ValueError(f"ARCTOPK_WIRE_DTYPE must be 'bf16' (or unset), got {env!r}")
+        self.wire_dtype = torch.bfloat16 if env == "bf16" else None
+        self.wire16_calls = 0  # compressed calls of fp32 buckets whose packed values went out as bf16
+
+    def _wire16(self, bucket_dtype) -> bool:
+        """Whether this call sends an fp32 bucket's packed values as bf16.  ValueError for a
+        ``wire_dtype`` other than None / torch.bfloat16, and for ``host_staged`` with it (the staged
+        byte count would be that of the fp32 values); ignored for bf16 buckets."""
+        wd = self.wire_dtype
+        if wd is None:
+            return False
+        if wd is not torch.bfloat16:
+            raise ValueError(f"wire_dtype must be None or torch.bfloat16, got {wd!r}")
+        if bucket_dtype != torch.float32:
+            return False
+        if self.host_staged:
+            raise ValueError("wire_dtype=torch.bfloat16 does not run with host_staged=True: the staged "
+                             "copy moves the fp32 packed values")
+        return True
 
     def _fp32_residual_option(self, name: str) -> bool:
         """Whether the residual-dtype option `name` is torch.float32; ValueError unless it is that
@@ -723,6 +756,9 @@ class GroupTopKState(HookState):
         out["error_dtype"] = "fp32" if self.error_dtype is torch.float32 else None
         out["mixed_buckets"] = sorted(self._mixed_buckets)
         out["ef21_error_dtype"] = "fp32" if self.ef21_error_dtype is torch.float32 else None
+        # for information: the residuals of an fp32 bucket are fp32 either way, so a checkpoint loads
+        # under either setting
+        out["wire_dtype"] = "bf16" if self.wire_dtype is torch.bfloat16 else None
         return out
 
     def load_state_dict(self, sd: dict, device=None) -> None:
@@ -822,6 +858,8 @@ class GroupTopKState(HookState):
             for c in (self._comms[2], self._comms[3]):  # (callback communicators keep views by address)
                 c.unregister(hit[1].sketch)
                 c.unregister(hit[1].packed)
+                if hit[1].packed16 is not None:
+                    c.unregister(hit[1].packed16)
         plan = BucketPlan(shapes, self.r, ratio, buf.dtype, buf.device, flags)
         self._plans[bucket.index()] = (key, plan, ident)
         return plan
@@ -1243,6 +1281,75 @@ def _mixed_call(state: GroupTopKState, bucket, input_tensor: torch.Tensor, plan:
     return fut
 
 
+def _wire16_call(state: GroupTopKState, bucket, input_tensor: torch.Tensor, plan: BucketPlan, ef: int,
+                 err: Optional[torch.Tensor], gerr: Optional[torch.Tensor], err_in: bool, seed: int, group,
+                 world_size: int, sid: int) -> torch.futures.Future[torch.Tensor]:
+    """The compressed call of an fp32 bucket whose packed values travel as bf16 (wire_dtype,
+    DESIGN.md section 4f).  Phase by phase on the caller's stream,
+
+        encode -> all-reduce(sketch, fp32) -> select -> pack_wire16 -> all-reduce(packed16, bf16) -> decode_wire16
+
+    with the collectives on the state's exchange communicators (none at world size 1 unless
+    force_exchange or an emulated wire asks for them; the branch still packs to bf16 and decodes
+    from it, so one GPU produces what a rank of N would).  Encode and select are the default
+    path's: the sketch is fp32 and the selected rows are the default path's for the same residual
+    and inputs.  The pack sends b(X) and leaves the rounding remainder in the residual (EF14:
+    E = X - f(b(X)); EF21: E += f(b(D))); the decode forms the mean in fp32.  Not used here: the
+    one-call step, deferral, exchange groups, select streams, trailing steps, keys mode, the riding
+    pack, the fused finalize and the select drawing the next V; zero rows (err_in = 2) are never
+    claimed, since a selected row of EF14's residual keeps its rounding remainder.  The Future is
+    complete on return."""
+    dev = input_tensor.device
+    L = _LIB[0]
+    if state._x_pend:  # deferred steps of other buckets: their decodes first, in order
+        _order_after_exchange(state, dev)
+    if plan.packed16 is None:  # zero-filled: the alignment pads ride the all-reduce as zeros
+        plan.packed16 = torch.zeros(max(1, plan.info.packed_len), dtype=torch.bfloat16, device=dev)
+    comms = world_size > 1 or state.force_exchange or state.emulate_wire is not None
+    sk = pk = None
+    if comms:
+        sk, pk = state._exchange_comms(group, dev)
+        if plan.comm_registered is not pk:
+            sk.register(plan.sketch)
+            pk.register(plan.packed)
+            plan.comm_registered = pk
+        if plan.packed16_registered is not pk:
+            pk.register(plan.packed16)
+            plan.packed16_registered = pk
+    vslot, V = -1, plan.V_ring[0]
+    if state.projections == "device":
+        if _claim_projections(state, plan, seed, sid, dev):
+            N.check(L.arctopk_draw_projections(plan.handle, seed, V.data_ptr(), sid), "arctopk_draw_projections")
+    else:
+        vslot, V = _host_projections(state, plan, bucket, seed, input_tensor.dtype, dev,
+                                     torch.cuda.current_stream(dev))
+    plan.encode(input_tensor, err, ef, bool(err_in), V, sid)
+    if vslot >= 0:
+        plan.projection_consumed(vslot, torch.cuda.current_stream(dev))
+    if comms and plan.info.sketch_len:
+        sk.check(L.arctopk_comm_allreduce(sk.handle, plan.sketch.data_ptr(), int(plan.info.sketch_len),
+                                          N.F32, sid), "arctopk_comm_allreduce(sketch)")
+    plan.select(world_size, sid)
+    N.check(L.arctopk_pack_wire16(plan.handle, input_tensor.data_ptr(), N.ptr(err), ef, int(bool(err_in)),
+                                  plan.rowlist.data_ptr(), plan.slotmap.data_ptr(), plan.packed16.data_ptr(),
+                                  sid), "arctopk_pack_wire16")
+    if comms:
+        pk.check(L.arctopk_comm_allreduce(pk.handle, plan.packed16.data_ptr(), int(plan.info.packed_len),
+                                          N.BF16, sid), "arctopk_comm_allreduce(packed16)")
+    N.check(L.arctopk_decode_wire16(plan.handle, plan.packed16.data_ptr(), plan.slotmap.data_ptr(), world_size,
+                                    ef, N.ptr(gerr), input_tensor.data_ptr(), sid), "arctopk_decode_wire16")
+    state.wire16_calls += 1
+    # the sketch term of BucketPlan.bits_sum in fp32, the selected values in bf16 (:278)
+    sketch_elems = sum(s.n * plan.r if s.kind == N.SEG_SKETCH else s.n if s.kind == N.SEG_RAW else 0
+                       for s in plan.segments)
+    state.comm_bits_this_round += 2 * (world_size - 1) * (sketch_elems * 32 + int(plan.info.values_len) * 16)
+    state.maybe_increase_iter(bucket)
+    state._raise_if_comm_failed()
+    fut = torch.futures.Future()
+    fut.set_result(input_tensor)
+    return fut
+
+
 def group_topk_hook(state: GroupTopKState, bucket: dist.GradBucket
                     ) -> torch.futures.Future[torch.Tensor]:
     state.maybe_accumulate_momentum_on_bucket(bucket)
@@ -1269,6 +1376,8 @@ def group_topk_hook(state: GroupTopKState, bucket: dist.GradBucket
     # or both EF21 residuals in fp32 under one (state.ef21_error_dtype)
     mixed21 = state._mixed21_residual(input_tensor.dtype, ef)
     mixed = state._mixed_residual(input_tensor.dtype, ef)
+    # an fp32 bucket whose packed values travel as bf16 (state.wire_dtype)
+    wire16 = state._wire16(input_tensor.dtype)
     if ef == N.EF14:
         if b not in state.error_dict:
             logger.info("A zero tensor of length %s that represents local error is created.", total)
@@ -1322,6 +1431,8 @@ def group_topk_hook(state: GroupTopKState, bucket: dist.GradBucket
     zr = state._zr_take(b, plan, err, ef)
     if mixed or mixed21:
         return _mixed_call(state, bucket, input_tensor, plan, ef, err, gerr, err_in, seed, group, world_size, sid)
+    if wire16:
+        return _wire16_call(state, bucket, input_tensor, plan, ef, err, gerr, err_in, seed, group, world_size, sid)
     if not state.host_staged:
         # ONE native call per bucket (arctopk_exchange_step): the kernels, the collectives at
         # world size > 1 (or with force_exchange: the N > 1 code path over one-rank

@@ -466,10 +466,14 @@ struct arctopk_plan {
     int64_t zr_encodes;                 // encode launches that ran the zero-rows kernels (diagnostics)
     void* mx;                           // work tables of the fp32-residual phases (mixed_ef.hip), built by
                                         //   the plan's first arctopk_encode_mixed / arctopk_pack_mixed
+    void* w16;                          // work tables of the bf16-wire pack and decode of an fp32 plan
+                                        //   (wire16.hip), built by the plan's first call there
 };
 namespace arctopk {
 // frees a plan's fp32-residual work tables (arctopk_plan_destroy)
 void mixed_forget(arctopk_plan* p);
+// ... and its bf16-wire work tables
+void wire16_forget(arctopk_plan* p);
 // host bookkeeping of the plan, like the exchange step's x_* fields
 inline void zr_clear(const arctopk_plan* p) {
     if (p) const_cast<arctopk_plan*>(p)->zr_valid = 0;

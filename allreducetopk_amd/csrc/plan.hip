@@ -552,6 +552,7 @@ extern "C" int arctopk_plan_destroy(arctopk_plan* p) {
     if (p->d_dense) (void)hipFree(p->d_dense);
     if (p->d_part) (void)hipFree(p->d_part);
     arctopk::mixed_forget(p);
+    arctopk::wire16_forget(p);
     delete[] p->h_segs;
     delete[] p->h_pack_begin;
     arctopk::exchange_forget(p);  // before its events go

@@ -30,6 +30,10 @@ are the ops above.
 bf16 bucket whose EF21 residuals are both float32 tensors (``GroupTopKState.ef21_error_dtype``, DESIGN.md
 section 4e); the select between them is the op above.
 
+``torch.ops.arctopk.pack_wire16`` / ``decode_wire16`` are the pack and decode of an fp32 bucket whose
+packed values travel as bfloat16 (``GroupTopKState.wire_dtype``); encode and
+select are the ops above.
+
 Each op replaces the same reference code as the C entry point it calls (include/arctopk.h).
 """
 from __future__ import annotations
@@ -172,6 +176,41 @@ def decode_mixed21(plan: int, packed: torch.Tensor, slotmap: torch.Tensor, world
             "arctopk_decode_mixed21")
 
 
+def _check_wire16(what: str, packed: torch.Tensor, **fp32) -> None:
+    if packed.dtype != torch.bfloat16 or not packed.is_contiguous():
+        raise ValueError(f"{what}: the packed values must be a contiguous bfloat16 tensor")
+    n = None
+    for name, t in fp32.items():
+        if t is None:
+            continue
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != packed.device:
+            raise ValueError(f"{what}: {name} must be a contiguous float32 tensor on the packed values' device")
+        if n is not None and t.numel() != n:
+            raise ValueError(f"{what}: {name} must have the bucket's length")
+        n = t.numel()
+
+
+@torch.library.custom_op("arctopk::pack_wire16", mutates_args=("err", "packed"))
+def pack_wire16(plan: int, grad: Optional[torch.Tensor], err: Optional[torch.Tensor], ef: int, err_in: bool,
+                rowlist: torch.Tensor, slotmap: torch.Tensor, packed: torch.Tensor) -> None:
+    """Selected rows of an fp32 bucket -> bf16 packed values; the fp32 residual keeps the rounding
+    remainder (EF14: E = X - float(packed); EF21: E += float(packed)) (arctopk_pack_wire16)."""
+    _check_wire16("pack_wire16", packed, grad=grad, err=err)
+    N.check(N.lib().arctopk_pack_wire16(plan, _ptr(grad), _ptr(err), ef, int(err_in), rowlist.data_ptr(),
+                                        slotmap.data_ptr(), packed.data_ptr(), _stream(packed)),
+            "arctopk_pack_wire16")
+
+
+@torch.library.custom_op("arctopk::decode_wire16", mutates_args=("gerr", "out"))
+def decode_wire16(plan: int, packed: torch.Tensor, slotmap: torch.Tensor, world_size: int, ef: int,
+                  gerr: Optional[torch.Tensor], out: torch.Tensor) -> None:
+    """fp32 bucket := float(packed) / world_size on the selected rows, zero elsewhere; EF21: added
+    to the global residual, which is written everywhere (arctopk_decode_wire16)."""
+    _check_wire16("decode_wire16", packed, out=out, gerr=gerr)
+    N.check(N.lib().arctopk_decode_wire16(plan, packed.data_ptr(), slotmap.data_ptr(), world_size, ef,
+                                          _ptr(gerr), out.data_ptr(), _stream(out)), "arctopk_decode_wire16")
+
+
 # fake implementations: the ops only mutate their declared outputs
 @draw_projections.register_fake
 def _(plan, seed, V):
@@ -225,4 +264,14 @@ def _(plan, grad, err, rowlist, slotmap, packed):
 
 @decode_mixed21.register_fake
 def _(plan, packed, slotmap, world_size, gerr, out):
+    return None
+
+
+@pack_wire16.register_fake
+def _(plan, grad, err, ef, err_in, rowlist, slotmap, packed):
+    return None
+
+
+@decode_wire16.register_fake
+def _(plan, packed, slotmap, world_size, ef, gerr, out):
     return None

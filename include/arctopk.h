@@ -675,6 +675,50 @@ int arctopk_decode_mixed21(const arctopk_plan* plan, const void* packed_bf16, co
                            int32_t world_size, float* gerr_f32, void* out_bf16, void* stream);
 
 /*
+ * The packed values of an fp32 bucket sent as bf16: the pack and decode
+ * phases of an fp32 plan whose packed all-reduce carries `packed_bf16`, bf16 values in the plan's
+ * packed layout counted in elements (the same packed_off and packed_len: a segment's values start
+ * 8-B aligned, 16-B aligned only where packed_off % 8 == 0).  Bucket, residuals, sketch and
+ * projections are fp32; encode and select are arctopk_encode and arctopk_select.  f and b as above.
+ *   arctopk_pack_wire16   : every selected row (rowlist: arctopk_select's; every entry is checked
+ *       against the segment's rows), every selected element of a RAW segment and every element of a
+ *       DENSE segment:
+ *         NONE : packed = b(G)
+ *         EF14 : X read from E (the encode stored it; a DENSE segment forms X = G + E, err_in = 1,
+ *                or X = G, err_in = 0, here: one fp32 add); packed = b(X); E := X - f(packed), one
+ *                fp32 subtract (exact: the residual keeps the rounding remainder of what was sent);
+ *                other rows keep E = X
+ *         EF21 : D = G - E, one fp32 subtract; packed = b(D); E := E + f(packed), one fp32 add;
+ *                other rows are not touched
+ *       Neither the row list nor the slot map is written, and the plan's zero-rows record is not
+ *       set: err_in = 2 does not exist here, a selected row of E holds its remainder, not zero.
+ *   arctopk_decode_wire16 : `packed_bf16` holds the all-reduced values P; mean = f(P) / world_size,
+ *       the correctly rounded fp32 quotient, not rounded to bf16.
+ *         NONE, EF14 : out = mean on selected elements (slot map: arctopk_select's; every element of
+ *                a DENSE segment), 0 elsewhere
+ *         EF21 : gE := gE + mean on selected elements, one fp32 add; out = gE on every element; gE
+ *                of unselected rows is read and left as stored
+ *       Every element of `out` is written; `out` may be the bucket.
+ * At world size 1: EF14 leaves out + E_new == G + E_old on every element, bit for bit; EF21 leaves
+ * gE == E bit for bit after every call of a bucket whose first call set E = G, gE = out.
+ * ARCTOPK_EINVAL for a null plan or one that is not ARCTOPK_F32, ef outside NONE / EF14 / EF21,
+ * err_in outside {0, 1}, world_size < 1, a null pointer the mode needs (rowlist, slotmap, packed,
+ * out; err for EF14 and EF21; gerr for EF21; grad for NONE, for EF21, and for EF14 on a plan with
+ * DENSE segments), grad / err / gerr / out not 16-B aligned, or packed_bf16 not 8-B aligned; every
+ * check runs before any device call and nothing is enqueued when one fails.  Stream-ordered, no
+ * host synchronisation; the first of these calls on a plan builds its work tables (one allocation
+ * and copy, freed with the plan), every later one only enqueues.
+ * Replaces: the gathers (:70-71, :101-102), EF14's tensor.view(-1)[indices] = 0 (:124), EF21's
+ * zero_/index_put (:126-128) and error.add_(input_tensor) (:275), values_memory.div_(ws) (:281),
+ * input_tensor.zero_() (:284), the scatter (:131-141) and gE.add_/input.copy_ (:288-290), for
+ * values_memory (:261-263) carried as bf16 on the wire.
+ */
+int arctopk_pack_wire16(const arctopk_plan* plan, const void* grad, void* err, int32_t ef, int32_t err_in,
+                        const int32_t* rowlist, const int32_t* slotmap, void* packed_bf16, void* stream);
+int arctopk_decode_wire16(const arctopk_plan* plan, const void* packed_bf16, const int32_t* slotmap,
+                          int32_t world_size, int32_t ef, void* gerr, void* out, void* stream);
+
+/*
  * Device projections of one bucket call: for every SKETCH segment in bucket order,
  * V[v_off ..] = torch.randn(m, r, device=dev, dtype) as drawn by the reference on the GPU
  * right after torch.manual_seed(seed) (group_topk_hook_no_reshape.py:49, :79, :255):
