@@ -73,6 +73,7 @@ _SIGS = {
     "arctopk_select_draw": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
                                       c_uint64, c_void_p, c_void_p]),
     "arctopk_diag_zero_row_encodes": (c_int32, [c_void_p, ctypes.POINTER(c_int64)]),
+    "arctopk_diag_encode_tiles": (c_int32, [c_void_p, ctypes.POINTER(c_int64), c_int32]),
     "arctopk_plan_bind": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "arctopk_step": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
                                c_uint64, c_void_p, c_uint64, c_void_p, c_void_p]),

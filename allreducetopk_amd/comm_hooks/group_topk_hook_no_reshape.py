@@ -190,11 +190,15 @@ class BucketPlan:
         N.check(L.arctopk_plan_bind(handle, self.sketch.data_ptr(), self.rowlist.data_ptr(),
                                     self.slotmap.data_ptr(), self.packed.data_ptr(),
                                     self.V_ring[0].data_ptr()), "arctopk_plan_bind")
+        self.bits_sum = self.bits_of(self.segments, r, dtype)
+
+    @staticmethod
+    def bits_of(segments, r: int, dtype) -> int:
+        """bits_sum of one call: sketch P + selected values per tensor (:32, :57, :70, :119);
+        a DENSE tensor has no sketch (P_bits 0) and sends its n values (c4 :22-23)"""
         bits = dtype_bits(dtype)
-        # bits_sum of one call: sketch P + selected values per tensor (:32, :57, :70, :119);
-        # a DENSE tensor has no sketch (P_bits 0) and sends its n values (c4 :22-23)
-        self.bits_sum = sum(((s.n * r if s.kind == N.SEG_SKETCH else s.n if s.kind == N.SEG_RAW else 0)
-                             + s.k_rows * s.m) * bits for s in self.segments)
+        return sum(((s.n * r if s.kind == N.SEG_SKETCH else s.n if s.kind == N.SEG_RAW else 0)
+                    + s.k_rows * s.m) * bits for s in segments)
 
     V_RING = 4        # projection slots allocated up front per bucket
     V_RING_MAX = 32   # ... and at most (then the copy stream waits for the oldest reader)
@@ -336,6 +340,17 @@ class BucketPlan:
     def row_energy(self, world_size: int, out, stream: int):
         N.check(N.lib().arctopk_row_energy(self.handle, self.sketch.data_ptr(), world_size,
                                            out.data_ptr(), stream), "arctopk_row_energy")
+
+    ENCODE_TILE_FIELDS = ("raw", "tile", "row_vec", "row_scalar", "n_split", "keyed", "enc_short",
+                          "mixed_vlds", "mixed_vglobal")
+
+    def encode_tiles(self) -> dict:
+        """Which encode paths the plan holds (arctopk_diag_encode_tiles): tiles per mode, column-split
+        and keyed tensors, the short-row kernel, and the fp32-residual encode's tiles with V in LDS /
+        in global memory (-1 before those tables exist)."""
+        out = (N.c_int64 * len(self.ENCODE_TILE_FIELDS))()
+        N.check(N.lib().arctopk_diag_encode_tiles(self.handle, out, len(out)), "arctopk_diag_encode_tiles")
+        return dict(zip(self.ENCODE_TILE_FIELDS, (int(v) for v in out)))
 
     def groups(self, target_bytes: int):
         """The bucket cut into runs of consecutive tensors of about `target_bytes` each (the

@@ -374,6 +374,8 @@ struct arctopk_plan {
     int n_enc_e;
     int enc_lds_bytes;            // dynamic LDS of the encode launch
     int enc_short;                // no wave-per-row tile in the tables: k_encode_short
+    int enc_mode_tiles[4];        // tiles of d_enc per mode (index ENC_*; arctopk_diag_encode_tiles)
+    int n_keyed;                  // `keyed` segments (SegDev)
     int dense_err_in;             // err_in of the plan's last encode: a DENSE segment has no encode
                                   // tile, so EF14's X = G + E (err_in) or G is formed by its pack
                                   // (or the fused pack + decode) from the bucket and the residual
@@ -472,6 +474,9 @@ struct arctopk_plan {
 namespace arctopk {
 // frees a plan's fp32-residual work tables (arctopk_plan_destroy)
 void mixed_forget(arctopk_plan* p);
+// the row tiles of those tables' encode that stage V in LDS and that read it from global memory;
+// false before the tables exist (arctopk_diag_encode_tiles)
+bool mixed_tile_counts(const arctopk_plan* p, int64_t* vlds, int64_t* vglobal);
 // ... and its bf16-wire work tables
 void wire16_forget(arctopk_plan* p);
 // host bookkeeping of the plan, like the exchange step's x_* fields

@@ -110,6 +110,7 @@ struct MxTab {       // the plan's mixed work tables (device) and their sizes
     MxTile* d_dtiles;  // EF21's decode tiles (k_mx_decode21)
     int n_tiles, n_chunks, n_dtiles;
     int lds_bytes;   // dynamic LDS of the encode launch
+    int n_vlds, n_vglobal;  // row tiles of d_tiles with / without MX_VLDS (diagnostics)
 };
 
 __device__ __forceinline__ float bf_bits_f(uint32_t u16) { return __uint_as_float(u16 << 16); }
@@ -572,6 +573,9 @@ int mixed_table(const arctopk_plan* p, MxTab** out) {
     t->n_tiles = (int)tiles.size();
     t->n_chunks = (int)chunks.size();
     t->lds_bytes = lds;
+    t->n_vlds = t->n_vglobal = 0;
+    for (const MxTile& mt : tiles)
+        if (!(mt.flags & MX_RAW)) ++((mt.flags & MX_VLDS) ? t->n_vlds : t->n_vglobal);
     hipError_t e = hipSetDevice(p->device);
     if (e == hipSuccess) e = mixed_upload(tiles, &t->d_tiles);
     if (e == hipSuccess) e = mixed_upload(chunks, &t->d_chunks);
@@ -640,6 +644,13 @@ void mixed_forget(arctopk_plan* p) {
     if (!p->mx) return;
     mixed_free(static_cast<MxTab*>(p->mx));
     p->mx = nullptr;
+}
+bool mixed_tile_counts(const arctopk_plan* p, int64_t* vlds, int64_t* vglobal) {
+    if (!p->mx) return false;
+    const MxTab* t = static_cast<const MxTab*>(p->mx);
+    *vlds = t->n_vlds;
+    *vglobal = t->n_vglobal;
+    return true;
 }
 }  // namespace arctopk
 

@@ -333,9 +333,11 @@ extern "C" int arctopk_plan_create_ex(const int64_t* dims, const int32_t* ndims,
     // k_encode's occupancy (28 x [512, 512, 3, 3]: 14,336 tiles, 134 -> 139 us lean)
     p->enc_short = (int)enc.size() <= ARCTOPK_ENC_SHORT_MAX_TILES;
     for (const EncTile& et : enc) p->enc_short = p->enc_short && (et.mode == ENC_RAW || et.mode == ENC_TILE);
+    for (const EncTile& et : enc) ++p->enc_mode_tiles[et.mode];
     p->dec_lds_bytes = (int)dec_lds;
     p->n_small = (int)small_ids.size();
     for (const SegDev& g : dsegs) p->any_keyed = p->any_keyed || g.keyed;
+    for (const SegDev& g : dsegs) p->n_keyed += g.keyed ? 1 : 0;
     p->n_large = (int)large_ids.size();
     p->small_lds = (int)(((small_rows + 3) & ~3) * 4 + 16);
 #define ALLOC_COPY(dst, vec)                                                                  \
@@ -581,6 +583,18 @@ extern "C" int arctopk_plan_query(const arctopk_plan* p, arctopk_plan_info* info
 extern "C" int arctopk_plan_segment(const arctopk_plan* p, int32_t i, arctopk_segment* seg) {
     if (!p || !seg || i < 0 || i >= p->nseg) return ARCTOPK_EINVAL;
     *seg = p->h_segs[i];
+    return 0;
+}
+
+// Diagnostics: which encode paths the plan's default tile table holds (host-side counts only)
+extern "C" int arctopk_diag_encode_tiles(const arctopk_plan* p, int64_t* out, int32_t n) {
+    if (!p || !out || n < 1) return ARCTOPK_EINVAL;
+    int64_t vlds = -1, vglobal = -1;
+    if (p->dtype == ARCTOPK_BF16) (void)arctopk::mixed_tile_counts(p, &vlds, &vglobal);
+    const int64_t v[ARCTOPK_DIAG_ENCODE_TILES] = {
+        p->enc_mode_tiles[ENC_RAW], p->enc_mode_tiles[ENC_TILE], p->enc_mode_tiles[ENC_ROW_VEC],
+        p->enc_mode_tiles[ENC_ROW_SCALAR], p->n_split, p->n_keyed, p->enc_short, vlds, vglobal};
+    for (int i = 0; i < n && i < ARCTOPK_DIAG_ENCODE_TILES; ++i) out[i] = v[i];
     return 0;
 }
 

@@ -187,8 +187,12 @@ int arctopk_encode(const arctopk_plan* plan, const void* grad, void* err, int32_
 
 /*
  * K2 select.  From the all-reduced sketch: P /= world_size, row energy
- * sum_j P[row][j]^2 (sequential j, as torch.sum over dim 1 for r <= 4) or P^2
- * (RAW), top-k_rows rows per segment.  Ties at the k-th energy: lowest rows
+ * sum_j P[row][j]^2 or P^2 (RAW), top-k_rows rows per segment.  The sum is
+ * sequential in j, ((q0 + q1) + q2) + ..., in fp32 (bf16: bf16 squares, the sum
+ * rounded once): the bits of torch's CPU sum over dim 1 for r <= 4 in both
+ * dtypes and for fp32 r = 8.  torch adds in another order for fp32 r = 5, 6, 7
+ * (last bits, at most 2 (r - 1) 2^-24 relative) and for bf16 r = 5 .. 8 (one
+ * bf16 step, on the rare row whose sum lies at a rounding boundary).  Ties at the k-th energy: lowest rows
  * first.  Writes the selected rows ascending (rowlist[sel_off ..]) and, for every
  * row, its packed slot or -1 (slotmap[row_off + row]).
  * Replaces: P /= ws; norms = sum(P**2, 1); torch.topk(norms, k, sorted=False);
@@ -803,6 +807,19 @@ int arctopk_diag_host_times(int64_t* ns, int32_t n, int64_t* calls);
 /* Encode launches of `plan` so far that ran the zero-rows kernel (err_in = 2 accepted; see
  * arctopk_encode).  Tests use it to show the path was taken or refused. */
 int arctopk_diag_zero_row_encodes(const arctopk_plan* plan, int64_t* count);
+/* Which encode paths `plan` holds, from its host-side bookkeeping (nothing is launched):
+ * out[0 .. min(n, ARCTOPK_DIAG_ENCODE_TILES)) =
+ *   [0] .. [3]  encode tiles of the plan's default table per mode: 1-D pass-through (RAW),
+ *               thread-per-row LDS tile, wave-per-row with 16-byte loads, wave-per-row scalar;
+ *   [4]         column-split tensors;
+ *   [5]         tensors whose encode writes select keys (world size 1);
+ *   [6]         1 when the table runs the short-row encode kernel, else 0;
+ *   [7], [8]    a bf16 plan's fp32-residual encode (arctopk_encode_mixed / _mixed21): row tiles
+ *               that stage V in LDS, and row tiles that read V from global memory; both -1
+ *               before the plan's first fp32-residual call built those tables, and for fp32 plans.
+ * Tests use it to show that a shape set reaches the paths it was chosen for. */
+#define ARCTOPK_DIAG_ENCODE_TILES 9
+int arctopk_diag_encode_tiles(const arctopk_plan* plan, int64_t* out, int32_t n);
 
 /* library build identification (for smoke tests) */
 const char* arctopk_version(void);

@@ -59,15 +59,16 @@ class ArcRun:
     """Drives one GroupTopKState over a sequence of calls per bucket and replays every
     compressed call through the oracle (single rank)."""
 
-    def __init__(self, ef, seed=1234, force_exchange=False, select_streams=None):
+    def __init__(self, ef, seed=1234, force_exchange=False, select_streams=None, r=4):
         self.ef = ef
-        self.st = GroupTopKState(None, r=4, compress_ratio=0.2, start_compress_iter=0,
+        self.r = r
+        self.st = GroupTopKState(None, r=r, compress_ratio=0.2, start_compress_iter=0,
                                  use_error_feedback=ef, seed=seed)
         self.st.force_exchange = force_exchange
         if select_streams is not None:  # default: the state's ("auto": select streams for <= 64 MiB)
             self.st.select_streams = select_streams
         self.st.defer_decode = True  # every bucket's Future is waited after the last one, as DDP does
-        self.ost = A.OracleState(r=4, compress_ratio=0.2, start_compress_iter=0,
+        self.ost = A.OracleState(r=r, compress_ratio=0.2, start_compress_iter=0,
                                  use_error_feedback=ef, seed=seed)
         self.E, self.gE = {}, {}
         self.flips = 0
@@ -93,7 +94,7 @@ class ArcRun:
             plan = self.st._plans[b][1]
             rows = _rows(plan)
             E_prev = self.E.get(b) if self.ef != "noef" else None
-            res = A.simulate_step([G], [E_prev], self.gE.get(b), shapes, 0.2, 4, self.ef, seed,
+            res = A.simulate_step([G], [E_prev], self.gE.get(b), shapes, 0.2, self.r, self.ef, seed,
                                   rows_override=rows, proj_device=DEV)
             for r_, nrm, s in zip(rows, res["norms"], plan.segments):
                 self.flips += check_rows_tie_aware(r_, nrm, int(s.k_rows), band=2e-4)

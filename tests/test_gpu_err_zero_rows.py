@@ -62,8 +62,8 @@ def zr_count(plan) -> int:
     return int(c.value)
 
 
-def make_state(on, force_exchange=False, seed=1234, ratio=0.2):
-    st = GroupTopKState(None, r=4, compress_ratio=ratio, start_compress_iter=0, use_error_feedback="ef14",
+def make_state(on, force_exchange=False, seed=1234, ratio=0.2, r=4):
+    st = GroupTopKState(None, r=r, compress_ratio=ratio, start_compress_iter=0, use_error_feedback="ef14",
                         seed=seed)
     st.force_exchange = force_exchange
     st.defer_decode = True  # Futures waited after the backward's last bucket, as DDP does
