@@ -38,7 +38,7 @@ import logging
 import os
 import time
 import weakref
-from typing import Dict, List, Optional, Tuple
+from typing import Callable, Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 import torch.distributed as dist
@@ -1221,148 +1221,168 @@ def _stage_through_host(state: GroupTopKState, pv: torch.Tensor, stream, dev,
     stream.wait_stream(d2h)
 
 
-def _mixed_call(state: GroupTopKState, bucket, input_tensor: torch.Tensor, plan: BucketPlan, ef: int,
-                err: torch.Tensor, gerr: Optional[torch.Tensor], err_in: bool, seed: int, group,
-                world_size: int, sid: int) -> torch.futures.Future[torch.Tensor]:
-    """The compressed call of a bf16 bucket whose residuals are fp32: EF14's `err` (error_dtype,
-    DESIGN.md section 4d; `gerr` is None) or EF21's `err` (E) and `gerr` (gE) (ef21_error_dtype,
-    section 4e).  Phase by phase on the caller's stream,
+def _done(input_tensor: torch.Tensor) -> torch.futures.Future[torch.Tensor]:
+    """A completed Future holding the bucket (reference :294-297)."""
+    fut = torch.futures.Future()
+    fut.set_result(input_tensor)
+    return fut
 
-        EF14: encode_mixed   -> all-reduce(sketch) -> select -> pack_mixed   -> all-reduce(packed) -> decode
-        EF21: encode_mixed21 -> all-reduce(sketch) -> select -> pack_mixed21 -> all-reduce(packed) -> decode_mixed21
 
-    with the collectives on the state's exchange communicators (none at world size 1 unless
-    force_exchange or an emulated wire asks for them).  EF21's encode only reads E; its pack adds
-    what it sent to E; its decode adds the fp32 mean to gE and writes b(gE) over the bucket.  Not
-    used here: the one-call step, deferral, exchange groups, select streams, trailing steps, keys
-    mode, the riding pack and the fused finalize; zero rows (err_in = 2) are never claimed, since a
-    selected row of EF14's residual keeps its rounding remainder.  The Future is complete on return."""
-    dev = input_tensor.device
-    b = bucket.index()
-    L = _LIB[0]
-    ef21 = ef == N.EF21
-    if state._x_pend:  # deferred steps of other buckets: their decodes first, in order
-        _order_after_exchange(state, dev)
-    comms = world_size > 1 or state.force_exchange or state.emulate_wire is not None
-    sk = pk = None
-    if comms:
-        sk, pk = state._exchange_comms(group, dev)
-        if plan.comm_registered is not pk:
-            sk.register(plan.sketch)
-            pk.register(plan.packed)
-            plan.comm_registered = pk
-    vslot, V = -1, plan.V_ring[0]
+def _register_comm_buffers(plan, sk, pk, packed16: bool = False) -> None:
+    """Make the sketch and packed buffers of `plan` (a bucket's or a group's) known to the exchange
+    communicators, once per plan and packed communicator; `packed16`: its bf16 packed values too."""
+    if plan.comm_registered is not pk:
+        sk.register(plan.sketch)
+        pk.register(plan.packed)
+        plan.comm_registered = pk
+    if packed16 and plan.packed16_registered is not pk:
+        pk.register(plan.packed16)
+        plan.packed16_registered = pk
+
+
+def _call_projections(state, plan, bucket, seed: int, sid: int, dev, dtype):
+    """This call's V: (ring slot, V, draw).  Device projections: (-1, None, draw), V is the plan's
+    V_ring[0], claimed, and `draw` tells whether it must still be drawn for `seed`; host projections:
+    staged into a ring slot."""
     if state.projections == "device":
-        if _claim_projections(state, plan, seed, sid, dev):
-            N.check(L.arctopk_draw_projections(plan.handle, seed, V.data_ptr(), sid), "arctopk_draw_projections")
-    else:
-        vslot, V = _host_projections(state, plan, bucket, seed, input_tensor.dtype, dev,
-                                     torch.cuda.current_stream(dev))
-    if ef21:
-        N.check(L.arctopk_encode_mixed21(plan.handle, input_tensor.data_ptr(), err.data_ptr(), V.data_ptr(),
-                                         plan.sketch.data_ptr(), sid), "arctopk_encode_mixed21")
-    else:
-        N.check(L.arctopk_encode_mixed(plan.handle, input_tensor.data_ptr(), err.data_ptr(), int(err_in),
-                                       V.data_ptr(), plan.sketch.data_ptr(), sid), "arctopk_encode_mixed")
-    if vslot >= 0:
-        plan.projection_consumed(vslot, torch.cuda.current_stream(dev))
-    if comms and plan.info.sketch_len:
-        sk.check(L.arctopk_comm_allreduce(sk.handle, plan.sketch.data_ptr(), int(plan.info.sketch_len),
-                                          N.BF16, sid), "arctopk_comm_allreduce(sketch)")
-    plan.select(world_size, sid)
-    if ef21:
-        N.check(L.arctopk_pack_mixed21(plan.handle, input_tensor.data_ptr(), err.data_ptr(),
-                                       plan.rowlist.data_ptr(), plan.slotmap.data_ptr(), plan.packed.data_ptr(),
-                                       sid), "arctopk_pack_mixed21")
-    else:
-        N.check(L.arctopk_pack_mixed(plan.handle, input_tensor.data_ptr(), err.data_ptr(), int(err_in),
-                                     plan.rowlist.data_ptr(), plan.slotmap.data_ptr(), plan.packed.data_ptr(),
-                                     sid), "arctopk_pack_mixed")
-    if comms:
-        pk.check(L.arctopk_comm_allreduce(pk.handle, plan.packed.data_ptr(), int(plan.info.packed_len),
-                                          N.BF16, sid), "arctopk_comm_allreduce(packed)")
-    if ef21:
-        N.check(L.arctopk_decode_mixed21(plan.handle, plan.packed.data_ptr(), plan.slotmap.data_ptr(), world_size,
-                                         gerr.data_ptr(), input_tensor.data_ptr(), sid), "arctopk_decode_mixed21")
-    else:
-        plan.decode(world_size, N.EF14, None, input_tensor, sid)
+        return -1, None, _claim_projections(state, plan, seed, sid, dev)
+    vslot, V = _host_projections(state, plan, bucket, seed, dtype, dev, torch.cuda.current_stream(dev))
+    return vslot, V, False
+
+
+# ---- the phase-by-phase paths: fp32 residuals under a bf16 bucket, bf16 packed values of an fp32 one ----
+def _encode_fp32_ef14(L, plan, x, err, ef, err_in, V, sid):
+    N.check(L.arctopk_encode_mixed(plan.handle, x.data_ptr(), err.data_ptr(), int(err_in), V.data_ptr(),
+                                   plan.sketch.data_ptr(), sid), "arctopk_encode_mixed")
+
+
+def _pack_fp32_ef14(L, plan, x, err, ef, err_in, packed, sid):
+    N.check(L.arctopk_pack_mixed(plan.handle, x.data_ptr(), err.data_ptr(), int(err_in), plan.rowlist.data_ptr(),
+                                 plan.slotmap.data_ptr(), packed.data_ptr(), sid), "arctopk_pack_mixed")
+
+
+def _decode_fp32_ef14(L, plan, world_size, ef, gerr, x, packed, sid):
+    plan.decode(world_size, N.EF14, None, x, sid)  # the plan's own: the bf16 mean of plan.packed
+
+
+def _encode_fp32_ef21(L, plan, x, err, ef, err_in, V, sid):
+    N.check(L.arctopk_encode_mixed21(plan.handle, x.data_ptr(), err.data_ptr(), V.data_ptr(),
+                                     plan.sketch.data_ptr(), sid), "arctopk_encode_mixed21")
+
+
+def _pack_fp32_ef21(L, plan, x, err, ef, err_in, packed, sid):
+    N.check(L.arctopk_pack_mixed21(plan.handle, x.data_ptr(), err.data_ptr(), plan.rowlist.data_ptr(),
+                                   plan.slotmap.data_ptr(), packed.data_ptr(), sid), "arctopk_pack_mixed21")
+
+
+def _decode_fp32_ef21(L, plan, world_size, ef, gerr, x, packed, sid):
+    N.check(L.arctopk_decode_mixed21(plan.handle, packed.data_ptr(), plan.slotmap.data_ptr(), world_size,
+                                     gerr.data_ptr(), x.data_ptr(), sid), "arctopk_decode_mixed21")
+
+
+def _encode_wire16(L, plan, x, err, ef, err_in, V, sid):
+    plan.encode(x, err, ef, bool(err_in), V, sid)  # the default path's: fp32 sketch, the same rows
+
+
+def _pack_wire16(L, plan, x, err, ef, err_in, packed, sid):
+    N.check(L.arctopk_pack_wire16(plan.handle, x.data_ptr(), N.ptr(err), ef, int(bool(err_in)),
+                                  plan.rowlist.data_ptr(), plan.slotmap.data_ptr(), packed.data_ptr(), sid),
+            "arctopk_pack_wire16")
+
+
+def _decode_wire16(L, plan, world_size, ef, gerr, x, packed, sid):
+    N.check(L.arctopk_decode_wire16(plan.handle, packed.data_ptr(), plan.slotmap.data_ptr(), world_size, ef,
+                                    N.ptr(gerr), x.data_ptr(), sid), "arctopk_decode_wire16")
+
+
+def _count_fp32_residual(state, b: int, plan) -> int:
+    """Counts the call and its bucket; the bits are the base hook's."""
     state._mixed_buckets.add(int(b))
     state.mixed_calls += 1
-    state.comm_bits_this_round += 2 * (world_size - 1) * plan.bits_sum  # (:278)
-    state.maybe_increase_iter(bucket)
-    state._raise_if_comm_failed()
-    fut = torch.futures.Future()
-    fut.set_result(input_tensor)
-    return fut
+    return plan.bits_sum
 
 
-def _wire16_call(state: GroupTopKState, bucket, input_tensor: torch.Tensor, plan: BucketPlan, ef: int,
-                 err: Optional[torch.Tensor], gerr: Optional[torch.Tensor], err_in: bool, seed: int, group,
-                 world_size: int, sid: int) -> torch.futures.Future[torch.Tensor]:
-    """The compressed call of an fp32 bucket whose packed values travel as bf16 (wire_dtype,
-    DESIGN.md section 4f).  Phase by phase on the caller's stream,
+def _count_wire16(state, b: int, plan) -> int:
+    """Counts the call; the sketch term of BucketPlan.bits_sum in fp32, the selected values in bf16."""
+    state.wire16_calls += 1
+    sketch_elems = sum(s.n * plan.r if s.kind == N.SEG_SKETCH else s.n if s.kind == N.SEG_RAW else 0
+                       for s in plan.segments)
+    return sketch_elems * 32 + int(plan.info.values_len) * 16
 
-        encode -> all-reduce(sketch, fp32) -> select -> pack_wire16 -> all-reduce(packed16, bf16) -> decode_wire16
+
+class PhasedPath(NamedTuple):
+    """What one phase-by-phase path of `_phased_call` differs in from the others."""
+    encode: Callable      # (L, plan, bucket tensor, err, ef, err_in, V, stream)
+    pack: Callable        # (L, plan, bucket tensor, err, ef, err_in, packed buffer, stream)
+    decode: Callable      # (L, plan, world size, ef, gerr, bucket tensor, packed buffer, stream)
+    sketch_wire: int      # dtype code of the sketch all-reduce
+    packed_wire: int      # ... and of the packed values'
+    packed16: bool        # the packed buffer is plan.packed16 (bf16, made by the plan's first call) not plan.packed
+    count: Callable       # (state, bucket index, plan): bumps the path's counters; the bits_sum of the call (:278)
+
+
+# EF14 with an fp32 residual under a bf16 bucket (error_dtype, DESIGN.md section 4d): gerr is None
+_FP32_EF14 = PhasedPath(_encode_fp32_ef14, _pack_fp32_ef14, _decode_fp32_ef14, N.BF16, N.BF16, False,
+                        _count_fp32_residual)
+# EF21 with E and gE in fp32 under a bf16 bucket (ef21_error_dtype, section 4e): the encode only reads E,
+# the pack adds what it sent to E, the decode adds the fp32 mean to gE and writes b(gE) over the bucket
+_FP32_EF21 = PhasedPath(_encode_fp32_ef21, _pack_fp32_ef21, _decode_fp32_ef21, N.BF16, N.BF16, False,
+                        _count_fp32_residual)
+# an fp32 bucket whose packed values travel as bf16 (wire_dtype, section 4f): encode and select are the
+# default path's; the pack sends b(X) and leaves the rounding remainder in the residual (EF14:
+# E = X - f(b(X)); EF21: E += f(b(D))); the decode forms the mean in fp32
+_WIRE16 = PhasedPath(_encode_wire16, _pack_wire16, _decode_wire16, N.F32, N.BF16, True, _count_wire16)
+
+
+def _phased_call(path: PhasedPath, state: GroupTopKState, bucket, input_tensor: torch.Tensor, plan: BucketPlan,
+                 ef: int, err: Optional[torch.Tensor], gerr: Optional[torch.Tensor], err_in: bool, seed: int,
+                 group, world_size: int, sid: int) -> torch.futures.Future[torch.Tensor]:
+    """The compressed call of a bucket on one of the mixed-precision paths above, phase by phase on
+    the caller's stream:
+
+        encode -> all-reduce(sketch) -> select -> pack -> all-reduce(packed) -> decode
 
     with the collectives on the state's exchange communicators (none at world size 1 unless
-    force_exchange or an emulated wire asks for them; the branch still packs to bf16 and decodes
-    from it, so one GPU produces what a rank of N would).  Encode and select are the default
-    path's: the sketch is fp32 and the selected rows are the default path's for the same residual
-    and inputs.  The pack sends b(X) and leaves the rounding remainder in the residual (EF14:
-    E = X - f(b(X)); EF21: E += f(b(D))); the decode forms the mean in fp32.  Not used here: the
-    one-call step, deferral, exchange groups, select streams, trailing steps, keys mode, the riding
-    pack, the fused finalize and the select drawing the next V; zero rows (err_in = 2) are never
-    claimed, since a selected row of EF14's residual keeps its rounding remainder.  The Future is
-    complete on return."""
+    force_exchange or an emulated wire asks for them; the path's kernels run all the same, so one
+    GPU produces what a rank of N would).  Not used here: the one-call step, deferral, exchange
+    groups, select streams, trailing steps, keys mode, the riding pack, the fused finalize and the
+    select drawing the next V; zero rows (err_in = 2) are never claimed, since a selected row of
+    EF14's residual keeps its rounding remainder.  The Future is complete on return."""
     dev = input_tensor.device
     L = _LIB[0]
     if state._x_pend:  # deferred steps of other buckets: their decodes first, in order
         _order_after_exchange(state, dev)
-    if plan.packed16 is None:  # zero-filled: the alignment pads ride the all-reduce as zeros
-        plan.packed16 = torch.zeros(max(1, plan.info.packed_len), dtype=torch.bfloat16, device=dev)
+    packed = plan.packed
+    if path.packed16:
+        if plan.packed16 is None:  # zero-filled: the alignment pads ride the all-reduce as zeros
+            plan.packed16 = torch.zeros(max(1, plan.info.packed_len), dtype=torch.bfloat16, device=dev)
+        packed = plan.packed16
     comms = world_size > 1 or state.force_exchange or state.emulate_wire is not None
     sk = pk = None
     if comms:
         sk, pk = state._exchange_comms(group, dev)
-        if plan.comm_registered is not pk:
-            sk.register(plan.sketch)
-            pk.register(plan.packed)
-            plan.comm_registered = pk
-        if plan.packed16_registered is not pk:
-            pk.register(plan.packed16)
-            plan.packed16_registered = pk
-    vslot, V = -1, plan.V_ring[0]
-    if state.projections == "device":
-        if _claim_projections(state, plan, seed, sid, dev):
+        _register_comm_buffers(plan, sk, pk, path.packed16)
+    vslot, V, draw = _call_projections(state, plan, bucket, seed, sid, dev, input_tensor.dtype)
+    if V is None:
+        V = plan.V_ring[0]
+        if draw:
             N.check(L.arctopk_draw_projections(plan.handle, seed, V.data_ptr(), sid), "arctopk_draw_projections")
-    else:
-        vslot, V = _host_projections(state, plan, bucket, seed, input_tensor.dtype, dev,
-                                     torch.cuda.current_stream(dev))
-    plan.encode(input_tensor, err, ef, bool(err_in), V, sid)
+    path.encode(L, plan, input_tensor, err, ef, err_in, V, sid)
     if vslot >= 0:
         plan.projection_consumed(vslot, torch.cuda.current_stream(dev))
     if comms and plan.info.sketch_len:
         sk.check(L.arctopk_comm_allreduce(sk.handle, plan.sketch.data_ptr(), int(plan.info.sketch_len),
-                                          N.F32, sid), "arctopk_comm_allreduce(sketch)")
+                                          path.sketch_wire, sid), "arctopk_comm_allreduce(sketch)")
     plan.select(world_size, sid)
-    N.check(L.arctopk_pack_wire16(plan.handle, input_tensor.data_ptr(), N.ptr(err), ef, int(bool(err_in)),
-                                  plan.rowlist.data_ptr(), plan.slotmap.data_ptr(), plan.packed16.data_ptr(),
-                                  sid), "arctopk_pack_wire16")
+    path.pack(L, plan, input_tensor, err, ef, err_in, packed, sid)
     if comms:
-        pk.check(L.arctopk_comm_allreduce(pk.handle, plan.packed16.data_ptr(), int(plan.info.packed_len),
-                                          N.BF16, sid), "arctopk_comm_allreduce(packed16)")
-    N.check(L.arctopk_decode_wire16(plan.handle, plan.packed16.data_ptr(), plan.slotmap.data_ptr(), world_size,
-                                    ef, N.ptr(gerr), input_tensor.data_ptr(), sid), "arctopk_decode_wire16")
-    state.wire16_calls += 1
-    # the sketch term of BucketPlan.bits_sum in fp32, the selected values in bf16 (:278)
-    sketch_elems = sum(s.n * plan.r if s.kind == N.SEG_SKETCH else s.n if s.kind == N.SEG_RAW else 0
-                       for s in plan.segments)
-    state.comm_bits_this_round += 2 * (world_size - 1) * (sketch_elems * 32 + int(plan.info.values_len) * 16)
+        pk.check(L.arctopk_comm_allreduce(pk.handle, packed.data_ptr(), int(plan.info.packed_len),
+                                          path.packed_wire, sid), "arctopk_comm_allreduce(packed)")
+    path.decode(L, plan, world_size, ef, gerr, input_tensor, packed, sid)
+    state.comm_bits_this_round += 2 * (world_size - 1) * path.count(state, bucket.index(), plan)
     state.maybe_increase_iter(bucket)
     state._raise_if_comm_failed()
-    fut = torch.futures.Future()
-    fut.set_result(input_tensor)
-    return fut
+    return _done(input_tensor)
 
 
 def group_topk_hook(state: GroupTopKState, bucket: dist.GradBucket
@@ -1413,9 +1433,7 @@ def group_topk_hook(state: GroupTopKState, bucket: dist.GradBucket
             if mixed21:
                 state._mixed_buckets.add(int(b))
             state.maybe_increase_iter(bucket)
-            fut = torch.futures.Future()
-            fut.set_result(input_tensor)
-            return fut
+            return _done(input_tensor)
         err = state.error_dict[b]
         gerr = state.global_error_dict[b]
     if err is not None:
@@ -1444,10 +1462,9 @@ def group_topk_hook(state: GroupTopKState, bucket: dist.GradBucket
     L = _LIB[0]
     # EF14: may this call skip the rows its previous call zeroed?  (consumes the bucket's record)
     zr = state._zr_take(b, plan, err, ef)
-    if mixed or mixed21:
-        return _mixed_call(state, bucket, input_tensor, plan, ef, err, gerr, err_in, seed, group, world_size, sid)
-    if wire16:
-        return _wire16_call(state, bucket, input_tensor, plan, ef, err, gerr, err_in, seed, group, world_size, sid)
+    path = _FP32_EF21 if mixed21 else _FP32_EF14 if mixed else _WIRE16 if wire16 else None
+    if path is not None:
+        return _phased_call(path, state, bucket, input_tensor, plan, ef, err, gerr, err_in, seed, group, world_size, sid)
     if not state.host_staged:
         # ONE native call per bucket (arctopk_exchange_step): the kernels, the collectives at
         # world size > 1 (or with force_exchange: the N > 1 code path over one-rank
@@ -1456,17 +1473,11 @@ def group_topk_hook(state: GroupTopKState, bucket: dist.GradBucket
         sk = pk = None
         if comms:
             sk, pk = state._exchange_comms(group, dev)  # (a failed communicator: the step returns its status)
-            if plan.comm_registered is not pk:
-                sk.register(plan.sketch)
-                pk.register(plan.packed)
-                plan.comm_registered = pk
-        vslot, vptr, draw, nplan, nseed = -1, None, False, None, 0
-        if device_v:
-            draw = _claim_projections(state, plan, seed, sid, dev)
-            nplan, nseed = _predraw_target(state, b, dtype, dev, sid)
-        else:
-            vslot, V = _host_projections(state, plan, bucket, seed, dtype, dev, torch.cuda.current_stream(dev))
-            vptr = V.data_ptr()
+            _register_comm_buffers(plan, sk, pk)
+        vslot, V, draw = _call_projections(state, plan, bucket, seed, sid, dev, dtype)
+        # device V is drawn by the step itself (`draw`), the predicted next call's by its select
+        vptr = None if V is None else V.data_ptr()
+        nplan, nseed = _predraw_target(state, b, dtype, dev, sid) if device_v else (None, 0)
         # deferred except for the last bucket of a backward (nothing follows it), which then
         # finishes every earlier deferred decode: nothing is left in flight when it returns
         dd = state.defer_decode
@@ -1560,10 +1571,7 @@ def group_topk_hook(state: GroupTopKState, bucket: dist.GradBucket
             last_u = ui == nu - 1
             u_defer = defer if last_u else True  # a group's decode is finished by a later one
             if grouped:
-                if u.comm_registered is not pk:
-                    sk.register(u.sketch)
-                    pk.register(u.packed)
-                    u.comm_registered = pk
+                _register_comm_buffers(u, sk, pk)
                 off = u.offset * esz
                 u_x, u_e, u_g = x_p + off, (e_p + off if e_p else None), (g_p + off if g_p else None)
                 if device_v:  # V drawn by group 0 and then by each group's select for the next
@@ -1672,7 +1680,6 @@ def group_topk_hook(state: GroupTopKState, bucket: dist.GradBucket
     _ht("decode")
 
     state.maybe_increase_iter(bucket)
-    fut = torch.futures.Future()
-    fut.set_result(input_tensor)
+    fut = _done(input_tensor)
     _ht("tail")
     return fut

@@ -19,7 +19,8 @@
 //
 // Select is the plan's own (arctopk_select): every phase here reads or writes the plan's sketch and
 // packed layouts.  Nothing is shared with the bf16-residual kernels of arctopk_kernels.hip but the
-// plan's segment table.
+// plan's segment table; the table layouts, their host loops and the small bf16 / fp32 16-B helpers
+// are mixed_common.h's, shared with wire16.hip.
 //
 // Work mapping.  A plan gets one table of encode tiles, one of pack chunks and one of EF21 decode
 // tiles, built at its first call here (mixed_table; freed with the plan), so a phase is one launch
@@ -48,6 +49,7 @@
 #include <vector>
 
 #include "common.h"
+#include "mixed_common.h"
 
 namespace {
 
@@ -86,23 +88,9 @@ __device__ __forceinline__ float mx_x(float g, float e) {
     else return g;
 }
 
-struct MxTile {
-    int32_t seg;
-    int32_t flags;
-    int64_t row0;    // first row (RAW: first element)
-    int32_t nrows;   // rows (RAW: elements)
-    int32_t lanes;   // lanes per row
-    int32_t rstride; // the tile's rows are row0 + q * rstride, q < nrows: the tiles of a tensor
-    int32_t pad;     //   interleave, so the blocks in flight stream one advancing window of it
-};
-
-struct MxChunk {
-    int32_t seg;
-    int32_t mode;
-    int64_t j0;      // first selected row (DENSE: first element)
-    int32_t nj;      // selected rows (DENSE: elements)
-    int32_t pad;
-};
+using MxTile = RowTile;      // (mixed_common.h)
+using MxChunk = PackChunk;
+using MxScale = MeanScale;
 
 struct MxTab {       // the plan's mixed work tables (device) and their sizes
     MxTile* d_tiles;
@@ -113,16 +101,6 @@ struct MxTab {       // the plan's mixed work tables (device) and their sizes
     int n_vlds, n_vglobal;  // row tiles of d_tiles with / without MX_VLDS (diagnostics)
 };
 
-__device__ __forceinline__ float bf_bits_f(uint32_t u16) { return __uint_as_float(u16 << 16); }
-__device__ __forceinline__ uint16_t f_to_bf(float f) { return (uint16_t)(cvt_pk_bf16(f, 0.0f) & 0xFFFFu); }
-
-typedef float vf4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ vf4_t ld_f4_nt(const float* p) {
-    return __builtin_nontemporal_load(reinterpret_cast<const vf4_t*>(p));
-}
-__device__ __forceinline__ void st_f4_nt(float* p, vf4_t v) {
-    __builtin_nontemporal_store(v, reinterpret_cast<vf4_t*>(p));
-}
 // the 8 bf16 of a 16-B unit as floats
 __device__ __forceinline__ void unpack8(u4_t w, float (&x)[8]) {
     x[0] = __uint_as_float(w.x << 16), x[1] = __uint_as_float(w.x & 0xFFFF0000u);
@@ -370,13 +348,6 @@ __global__ void __launch_bounds__(kMxBlock) k_mx_pack(const SegDev* __restrict__
 }
 
 // ---- EF21 decode ---------------------------------------------------------------------------
-// mean of the all-reduced values: x / ws correctly rounded (Scale of arctopk_kernels.hip)
-struct MxScale {
-    float ws, inv;
-    int pow2;
-    __device__ __forceinline__ float operator()(float x) const { return pow2 ? x * inv : __fdiv_rn(x, ws); }
-};
-
 // One decode tile of rows: `lanes` lanes per row as in the encode, the row's slot read once.
 template <bool VEC>
 __device__ __forceinline__ void dec21_rows(const SegDev& s, const MxTile& t, const bf16_t* __restrict__ packed,
@@ -491,24 +462,11 @@ __global__ void __launch_bounds__(kMxBlock) k_mx_decode21(const SegDev* __restri
 }
 
 // ---- the plan's tables ---------------------------------------------------------------------
-// a device copy of v (one element allocated for an empty one)
-template <class T>
-hipError_t mixed_upload(const std::vector<T>& v, T** d) {
-    hipError_t e = hipMalloc((void**)d, std::max<size_t>(1, v.size()) * sizeof(T));
-    if (e == hipSuccess && !v.empty()) e = hipMemcpy(*d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-    return e;
-}
 void mixed_free(MxTab* t) {
     if (t->d_tiles) (void)hipFree(t->d_tiles);
     if (t->d_chunks) (void)hipFree(t->d_chunks);
     if (t->d_dtiles) (void)hipFree(t->d_dtiles);
     delete t;
-}
-
-int pow2_at_least(int64_t x) {
-    int p = 1;
-    while (p < x && p < 64) p <<= 1;
-    return p;
 }
 
 int mixed_table(const arctopk_plan* p, MxTab** out) {
@@ -529,40 +487,23 @@ int mixed_table(const arctopk_plan* p, MxTab** out) {
         const arctopk_segment& s = p->h_segs[i];
         const bool vec = s.m % 8 == 0 && s.offset % 8 == 0;
         if (s.kind == ARCTOPK_SEG_DENSE) {
-            for (int64_t e = 0; e < s.n; e += kMxPackElems)
-                chunks.push_back(MxChunk{i, MXP_DENSE, e, (int32_t)std::min<int64_t>(kMxPackElems, s.n - e), 0});
+            push_pack_chunks(chunks, i, MXP_DENSE, s.n, 1, kMxPackElems);
             const int dflags = MX_DENSE | ((s.offset % 8 == 0 && s.packed_off % 8 == 0) ? MX_VEC : 0);
-            for (int64_t e = 0; e < s.n; e += kMxPackElems)
-                dtiles.push_back(MxTile{i, dflags, e, (int32_t)std::min<int64_t>(kMxPackElems, s.n - e), 1, 1, 0});
+            push_range_tiles(dtiles, i, dflags, s.n, kMxPackElems);
             continue;
         }
         if (s.kind == ARCTOPK_SEG_RAW) {
-            for (int64_t e = 0; e < s.n; e += kMxRawElems)
-                tiles.push_back(MxTile{i, MX_RAW, e, (int32_t)std::min<int64_t>(kMxRawElems, s.n - e), 1, 1, 0});
+            push_range_tiles(tiles, i, MX_RAW, s.n, kMxRawElems);
         } else {
             const bool vlds = s.m * r * 4 <= (int64_t)kVLdsMaxBytes;
-            const int lanes = pow2_at_least(vec ? s.m / 8 : s.m);
-            const int groups = kMxBlock / lanes;
-            // whole rounds of the block's groups, at least one
-            int64_t per = std::max<int64_t>(1, tile_elems / s.m);
-            per = std::max<int64_t>(groups, per / groups * groups);
             const int flags = (vec ? MX_VEC : 0) | (vlds ? MX_VLDS : 0);
-            // tile ti holds rows ti, ti + ntiles, ...: consecutive blocks read adjacent rows
-            const int64_t ntiles = (s.n + per - 1) / per;
-            for (int64_t ti = 0; ti < ntiles; ++ti) {
-                tiles.push_back(MxTile{i, flags, ti, (int32_t)((s.n - ti + ntiles - 1) / ntiles), lanes,
-                                       (int32_t)ntiles, 0});
-                if (s.m > 2) dtiles.push_back(tiles.back());  // the decode walks the same rows
-            }
+            const int64_t ntiles = push_row_tiles(tiles, i, flags, s.n, s.m, vec, 8, kMxBlock, tile_elems);
+            if (s.m > 2) dtiles.insert(dtiles.end(), tiles.end() - ntiles, tiles.end());  // the decode walks the same rows
             if (vlds) lds = std::max<int>(lds, (int)(((s.m + 7) & ~int64_t(7)) * r * 2));
         }
         if (s.m <= 2)  // RAW tensors and rows of one or two columns: a decode thread per row
-            for (int64_t e = 0; e < s.n; e += kMxRawElems)
-                dtiles.push_back(MxTile{i, MX_SHORT, e, (int32_t)std::min<int64_t>(kMxRawElems, s.n - e), 1, 1, 0});
-        const int64_t per = std::max<int64_t>(1, kMxPackElems / s.m);
-        for (int64_t j = 0; j < s.k_rows; j += per)
-            chunks.push_back(MxChunk{i, vec ? MXP_ROWS_VEC : MXP_ROWS, j,
-                                     (int32_t)std::min<int64_t>(per, s.k_rows - j), 0});
+            push_range_tiles(dtiles, i, MX_SHORT, s.n, kMxRawElems);
+        push_pack_chunks(chunks, i, vec ? MXP_ROWS_VEC : MXP_ROWS, s.k_rows, s.m, kMxPackElems);
     }
     MxTab* t = new (std::nothrow) MxTab;
     if (!t) return ARCTOPK_EINVAL;
@@ -577,9 +518,9 @@ int mixed_table(const arctopk_plan* p, MxTab** out) {
     for (const MxTile& mt : tiles)
         if (!(mt.flags & MX_RAW)) ++((mt.flags & MX_VLDS) ? t->n_vlds : t->n_vglobal);
     hipError_t e = hipSetDevice(p->device);
-    if (e == hipSuccess) e = mixed_upload(tiles, &t->d_tiles);
-    if (e == hipSuccess) e = mixed_upload(chunks, &t->d_chunks);
-    if (e == hipSuccess) e = mixed_upload(dtiles, &t->d_dtiles);
+    if (e == hipSuccess) e = upload(tiles, &t->d_tiles);
+    if (e == hipSuccess) e = upload(chunks, &t->d_chunks);
+    if (e == hipSuccess) e = upload(dtiles, &t->d_dtiles);
     if (e != hipSuccess) {
         mixed_free(t);
         return (int)e;
@@ -600,7 +541,6 @@ int mixed_begin(const arctopk_plan* p, uintptr_t misaligned, int MxTab::*count, 
     if (st == 0 && t->*count > 0) *out = t;
     return st;
 }
-uintptr_t low_bits(const void* a, uintptr_t mask) { return (uintptr_t)a & mask; }
 
 template <int MODE>
 int mixed_encode(const arctopk_plan* p, const void* grad, mx_err_t<MODE>* err, const void* V, void* sketch,
@@ -684,11 +624,8 @@ extern "C" int arctopk_decode_mixed21(const arctopk_plan* p, const void* packed,
     MxTab* t = nullptr;
     const int st = mixed_begin(p, low_bits(packed, 15) | low_bits(gerr, 15) | low_bits(out, 15), &MxTab::n_dtiles, &t);
     if (!t) return st;
-    MxScale sc;
-    sc.ws = (float)world_size;
-    sc.pow2 = (world_size & (world_size - 1)) == 0;
-    sc.inv = 1.0f / (float)world_size;
     hipLaunchKernelGGL(k_mx_decode21, dim3((unsigned)t->n_dtiles), dim3(kMxBlock), 0, (hipStream_t)stream, p->d_segs,
-                       t->d_dtiles, static_cast<const bf16_t*>(packed), slotmap, sc, gerr, static_cast<bf16_t*>(out));
+                       t->d_dtiles, static_cast<const bf16_t*>(packed), slotmap, make_mean_scale(world_size), gerr,
+                       static_cast<bf16_t*>(out));
     return (int)hipGetLastError();
 }

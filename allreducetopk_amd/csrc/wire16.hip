@@ -15,9 +15,10 @@
 //
 // Encode and select are the plan's own (arctopk_encode, arctopk_select).  `packed` has the plan's
 // packed layout in elements, so a segment's bf16 values start 8-B aligned (packed_off % 4 == 0) and
-// 16-B aligned only where packed_off % 8 == 0.  Nothing is shared with the other kernels of the
-// library but the plan's segment table; the plan's zero-rows record is not set (a selected row of E
-// holds its remainder, not zero).
+// 16-B aligned only where packed_off % 8 == 0.  The kernels share nothing with the library's other
+// kernels but the plan's segment table; the table layouts, their host loops and the small bf16 /
+// fp32 16-B helpers are mixed_common.h's, shared with mixed_ef.hip.  The plan's zero-rows record is
+// not set (a selected row of E holds its remainder, not zero).
 //
 // Work mapping.  A plan gets one table of pack chunks and one of decode tiles at its first call
 // here (w16_table; freed with the plan), so a phase is one launch and no copy.
@@ -41,13 +42,14 @@
 #include <vector>
 
 #include "common.h"
+#include "mixed_common.h"
 
 namespace {
 
 using namespace arctopk;
 
 constexpr int kW16Block = 256;
-constexpr int64_t kW16PackElems = 8192;   // elements per pack chunk (kMxPackElems of mixed_ef.hip)
+constexpr int64_t kW16PackElems = 8192;   // elements per pack chunk (as mixed_ef.hip's)
 constexpr int64_t kW16ShortElems = 4096;  // rows per thread-per-row decode tile
 constexpr int kW16Units = 4;              // 16-B units of out a decode lane takes per step
 constexpr int64_t kW16DecElems = 8192;    // elements per decode row tile (common.h: ARCTOPK_DEC_CHUNK)
@@ -58,23 +60,10 @@ enum : int32_t { W16_VEC = 1, W16_SHORT = 2, W16_DENSE = 4, W16_FLAT = 8 };  // 
 // the residual rule of a kernel (the ARCTOPK_EF_* codes)
 enum W16Ef : int { W16_NONE = ARCTOPK_EF_NONE, W16_EF14 = ARCTOPK_EF14, W16_EF21 = ARCTOPK_EF21 };
 
-struct W16Chunk {
-    int32_t seg;
-    int32_t mode;
-    int64_t j0;      // first selected row (DENSE: first element)
-    int32_t nj;      // selected rows (DENSE: elements)
-    int32_t pad;
-};
-
-struct W16Tile {
-    int32_t seg;
-    int32_t flags;
-    int64_t row0;    // first row (DENSE: first element)
-    int32_t nrows;   // rows (DENSE: elements)
-    int32_t lanes;   // lanes per row
-    int32_t rstride; // the tile's rows are row0 + q * rstride, q < nrows (the tiles of a tensor interleave)
-    int32_t pad;
-};
+using W16Chunk = PackChunk;  // (mixed_common.h)
+using W16Tile = RowTile;
+using W16Scale = MeanScale;
+using wf4_t = vf4_t;
 
 struct W16Tab {      // the plan's work tables (device) and their sizes
     W16Chunk* d_chunks;
@@ -82,15 +71,6 @@ struct W16Tab {      // the plan's work tables (device) and their sizes
     int n_chunks, n_tiles;
 };
 
-typedef float wf4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ wf4_t ld_f4_nt(const float* p) {
-    return __builtin_nontemporal_load(reinterpret_cast<const wf4_t*>(p));
-}
-__device__ __forceinline__ void st_f4_nt(float* p, wf4_t v) {
-    __builtin_nontemporal_store(v, reinterpret_cast<wf4_t*>(p));
-}
-__device__ __forceinline__ float bf_bits_f(uint32_t u16) { return __uint_as_float(u16 << 16); }
-__device__ __forceinline__ uint16_t f_to_bf(float f) { return (uint16_t)(cvt_pk_bf16(f, 0.0f) & 0xFFFFu); }
 // the 4 bf16 of an 8-B unit as floats
 __device__ __forceinline__ wf4_t unpack4(u2_t w) {
     return wf4_t{__uint_as_float(w.x << 16), __uint_as_float(w.x & 0xFFFF0000u),
@@ -243,12 +223,6 @@ __global__ void __launch_bounds__(kW16Block) k_w16_pack(const SegDev* __restrict
 }
 
 // ---- decode --------------------------------------------------------------------------------
-// mean of the all-reduced values: x / ws correctly rounded (MxScale of mixed_ef.hip)
-struct W16Scale {
-    float ws, inv;
-    int pow2;
-    __device__ __forceinline__ float operator()(float x) const { return pow2 ? x * inv : __fdiv_rn(x, ws); }
-};
 __device__ __forceinline__ wf4_t w16_mean4(u2_t w, const W16Scale sc) {
     const wf4_t y = unpack4(w);
     return wf4_t{sc(y.x), sc(y.y), sc(y.z), sc(y.w)};
@@ -426,23 +400,10 @@ __global__ void __launch_bounds__(kW16Block) k_w16_decode(const SegDev* __restri
 }
 
 // ---- the plan's tables ---------------------------------------------------------------------
-// a device copy of v (one element allocated for an empty one)
-template <class T>
-hipError_t w16_upload(const std::vector<T>& v, T** d) {
-    hipError_t e = hipMalloc((void**)d, std::max<size_t>(1, v.size()) * sizeof(T));
-    if (e == hipSuccess && !v.empty()) e = hipMemcpy(*d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-    return e;
-}
 void w16_free(W16Tab* t) {
     if (t->d_chunks) (void)hipFree(t->d_chunks);
     if (t->d_tiles) (void)hipFree(t->d_tiles);
     delete t;
-}
-
-int w16_pow2_at_least(int64_t x) {
-    int p = 1;
-    while (p < x && p < 64) p <<= 1;
-    return p;
 }
 
 int w16_table(const arctopk_plan* p, W16Tab** out) {
@@ -456,37 +417,19 @@ int w16_table(const arctopk_plan* p, W16Tab** out) {
         const arctopk_segment& s = p->h_segs[i];
         const bool quad = s.offset % 4 == 0 && s.packed_off % 4 == 0;
         if (s.kind == ARCTOPK_SEG_DENSE) {
-            for (int64_t e = 0; e < s.n; e += kW16PackElems) {
-                const int32_t n = (int32_t)std::min<int64_t>(kW16PackElems, s.n - e);
-                chunks.push_back(W16Chunk{i, W16P_DENSE, e, n, 0});
-                tiles.push_back(W16Tile{i, W16_DENSE | (quad ? W16_VEC : 0), e, n, 1, 1, 0});
-            }
+            push_pack_chunks(chunks, i, W16P_DENSE, s.n, 1, kW16PackElems);
+            push_range_tiles(tiles, i, W16_DENSE | (quad ? W16_VEC : 0), s.n, kW16PackElems);
             continue;
         }
         const bool vec = quad && s.m % 4 == 0;  // (SegDev::vec)
         if (s.m < 4) {  // RAW tensors and rows of up to three columns: a decode thread per row
-            for (int64_t e = 0; e < s.n; e += kW16ShortElems)
-                tiles.push_back(W16Tile{i, W16_SHORT, e, (int32_t)std::min<int64_t>(kW16ShortElems, s.n - e), 1, 1, 0});
+            push_range_tiles(tiles, i, W16_SHORT, s.n, kW16ShortElems);
         } else if (!vec && s.m < kW16FlatMaxM) {  // short rows off the 16-B grid: contiguous row ranges
-            const int64_t per = std::max<int64_t>(1, kW16DecElems / s.m);
-            for (int64_t r0 = 0; r0 < s.n; r0 += per)
-                tiles.push_back(W16Tile{i, W16_FLAT, r0, (int32_t)std::min<int64_t>(per, s.n - r0), 1, 1, 0});
+            push_range_tiles(tiles, i, W16_FLAT, s.n, std::max<int64_t>(1, kW16DecElems / s.m));
         } else {
-            const int lanes = w16_pow2_at_least(vec ? s.m / 4 : s.m);
-            const int groups = kW16Block / lanes;
-            // whole rounds of the block's groups, at least one
-            int64_t per = std::max<int64_t>(1, kW16DecElems / s.m);
-            per = std::max<int64_t>(groups, per / groups * groups);
-            // tile ti holds rows ti, ti + ntiles, ...: consecutive blocks write adjacent rows
-            const int64_t ntiles = (s.n + per - 1) / per;
-            for (int64_t ti = 0; ti < ntiles; ++ti)
-                tiles.push_back(W16Tile{i, vec ? W16_VEC : 0, ti, (int32_t)((s.n - ti + ntiles - 1) / ntiles), lanes,
-                                        (int32_t)ntiles, 0});
+            push_row_tiles(tiles, i, vec ? W16_VEC : 0, s.n, s.m, vec, 4, kW16Block, kW16DecElems);
         }
-        const int64_t per = std::max<int64_t>(1, kW16PackElems / s.m);
-        for (int64_t j = 0; j < s.k_rows; j += per)
-            chunks.push_back(W16Chunk{i, vec ? W16P_ROWS_VEC : W16P_ROWS, j,
-                                      (int32_t)std::min<int64_t>(per, s.k_rows - j), 0});
+        push_pack_chunks(chunks, i, vec ? W16P_ROWS_VEC : W16P_ROWS, s.k_rows, s.m, kW16PackElems);
     }
     W16Tab* t = new (std::nothrow) W16Tab;
     if (!t) return ARCTOPK_EINVAL;
@@ -495,8 +438,8 @@ int w16_table(const arctopk_plan* p, W16Tab** out) {
     t->n_chunks = (int)chunks.size();
     t->n_tiles = (int)tiles.size();
     hipError_t e = hipSetDevice(p->device);
-    if (e == hipSuccess) e = w16_upload(chunks, &t->d_chunks);
-    if (e == hipSuccess) e = w16_upload(tiles, &t->d_tiles);
+    if (e == hipSuccess) e = upload(chunks, &t->d_chunks);
+    if (e == hipSuccess) e = upload(tiles, &t->d_tiles);
     if (e != hipSuccess) {
         w16_free(t);
         return (int)e;
@@ -505,9 +448,6 @@ int w16_table(const arctopk_plan* p, W16Tab** out) {
     *out = t;
     return 0;
 }
-
-uintptr_t low_bits(const void* a, uintptr_t mask) { return (uintptr_t)a & mask; }
-bool ef_known(int32_t ef) { return ef == ARCTOPK_EF_NONE || ef == ARCTOPK_EF14 || ef == ARCTOPK_EF21; }
 
 template <int EF>
 void launch_pack(const arctopk_plan* p, const W16Tab* t, const void* grad, void* err, int32_t err_in,
@@ -552,10 +492,7 @@ extern "C" int arctopk_decode_wire16(const arctopk_plan* p, const void* packed, 
     W16Tab* t = nullptr;
     const int st = w16_table(p, &t);
     if (st != 0 || t->n_tiles == 0) return st;
-    W16Scale sc;
-    sc.ws = (float)world_size;
-    sc.pow2 = (world_size & (world_size - 1)) == 0;
-    sc.inv = 1.0f / (float)world_size;
+    const W16Scale sc = make_mean_scale(world_size);
     const dim3 grid((unsigned)t->n_tiles), block(kW16Block);
     const bf16_t* pk = static_cast<const bf16_t*>(packed);
     if (ef == ARCTOPK_EF21)

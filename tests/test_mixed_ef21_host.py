@@ -310,3 +310,89 @@ def test_oracle_invariant_at_world_size_one(dense_1d):
         moved |= sent
         Es, gE = res["E_new"], res["gE_new"]
     assert moved.any() and not moved.all()
+
+
+# ---- the branch's collectives, pending deferred steps and bits ---------------------------------
+class _Comm:
+    handle = 1
+
+    def __init__(self):
+        self.registered = []
+
+    def register(self, t):
+        self.registered.append(t)
+
+    def check(self, status, what):
+        assert status == 0
+
+    def raise_if_failed(self):
+        pass
+
+
+def _with_comms(rig, st, ws=1):
+    """Stub exchange communicators for `st`, a group of `ws` ranks, and an all-reduce entry point
+    that records itself."""
+    st._test_comms = (_Comm(), _Comm())
+    st._exchange_comms = lambda group, dev: st._test_comms
+    st.process_group = types.SimpleNamespace(size=lambda: ws)
+    rig.lib.arctopk_comm_allreduce = lambda comm, buf, count, dtype, stream: rig.lib.calls.append(
+        ("allreduce", count, dtype)) or 0
+    return st
+
+
+def _branch_with_collectives(plan):
+    return ["encode_mixed21", ("allreduce", plan.info.sketch_len, N.BF16), "select", "pack_mixed21",
+            ("allreduce", plan.info.packed_len, N.BF16), "decode_mixed21"]
+
+
+@pytest.mark.parametrize("ws,force", [(1, True), (2, False)])
+def test_native_call_sequence_with_collectives(rig, ws, force):
+    st = rig.make()
+    st.ef21_error_dtype = FP32
+    st.force_exchange = force
+    _with_comms(rig, st, ws)
+    assert rig.call(st) == []  # the dense first call (torch's process group)
+    for _ in range(3):
+        calls = rig.call(st)
+        plan = rig.plans[(0, st._plan_ratio())]
+        assert calls == _branch_with_collectives(plan)
+    # the plan's buffers are registered once per plan, not once per call
+    sk, pk = st._test_comms
+    assert len(sk.registered) == 1 and sk.registered[0] is plan.sketch
+    assert len(pk.registered) == 1 and pk.registered[0] is plan.packed
+    assert plan.comm_registered is pk and st.mixed_calls == 3
+
+
+def test_no_collectives_without_communicators(rig):
+    st = rig.make()
+    st.ef21_error_dtype = FP32
+    _with_comms(rig, st, 1)  # world size 1, no force_exchange, no emulated wire
+    assert rig.call(st) == [] and rig.call(st) == BRANCH
+    assert not st._test_comms[0].registered and not st._test_comms[1].registered
+
+
+def test_pending_deferred_steps_are_finished_first(rig):
+    st = rig.make()
+    st.ef21_error_dtype = FP32
+    st.defer_decode = True
+    rig.lib.arctopk_exchange_finish = lambda *a: rig.lib.calls.append("exchange_finish") or 0
+    assert rig.call(st) == []  # bucket 0's dense first call
+    # default-path calls of another bucket (fp32: the option does not apply); the second defers its decode
+    G = torch.ones(bucket_numel(SHAPES), dtype=FP32)
+    assert H.group_topk_hook(st, SyntheticBucket(G, SHAPES, index=1, is_last=False)).done()
+    fut = H.group_topk_hook(st, SyntheticBucket(G, SHAPES, index=1, is_last=False))
+    assert not fut.done() and len(st._x_pend) == 1
+    assert rig.call(st) == ["exchange_finish"] + BRANCH
+    assert fut.done() and not st._x_pend
+
+
+def test_bits_at_world_size_two(rig):
+    st = rig.make()
+    st.ef21_error_dtype = FP32
+    _with_comms(rig, st, 2)
+    rig.call(st)
+    first = st.comm_bits_this_round
+    assert first == bucket_numel(SHAPES) * 16  # the dense first call's
+    rig.call(st)
+    plan = rig.plans[(0, st._plan_ratio())]
+    assert st.comm_bits_this_round - first == 2 * (2 - 1) * plan.bits_sum == 2000

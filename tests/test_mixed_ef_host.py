@@ -242,3 +242,80 @@ def test_oracle_conservation(dense_1d):
     # the bf16-residual rule cannot: it rounds X before it stores it
     Xb = G + E.to(BF16)
     assert not torch.equal(MX.f(Xb), MX.f(G) + E)
+
+
+# ---- the branch's collectives, pending deferred steps and bits ---------------------------------
+class _Comm:
+    handle = 1
+
+    def __init__(self):
+        self.registered = []
+
+    def register(self, t):
+        self.registered.append(t)
+
+    def check(self, status, what):
+        assert status == 0
+
+    def raise_if_failed(self):
+        pass
+
+
+def _with_comms(rig, st, ws=1):
+    """Stub exchange communicators for `st`, a group of `ws` ranks, and an all-reduce entry point
+    that records itself."""
+    st._test_comms = (_Comm(), _Comm())
+    st._exchange_comms = lambda group, dev: st._test_comms
+    st.process_group = types.SimpleNamespace(size=lambda: ws)
+    rig.lib.arctopk_comm_allreduce = lambda comm, buf, count, dtype, stream: rig.lib.calls.append(
+        ("allreduce", count, dtype)) or 0
+    return st
+
+
+@pytest.mark.parametrize("ws,force", [(1, True), (2, False)])
+def test_native_call_sequence_with_collectives(rig, ws, force):
+    st = rig.make()
+    st.error_dtype = torch.float32
+    st.force_exchange = force
+    _with_comms(rig, st, ws)
+    for err_in in (0, 1, 1):
+        calls = rig.call(st)
+        plan = rig.plans[(0, st._plan_ratio())]
+        assert calls == [("encode_mixed", err_in), ("allreduce", plan.info.sketch_len, N.BF16), ("select", ws),
+                         ("pack_mixed", err_in), ("allreduce", plan.info.packed_len, N.BF16), ("decode", N.EF14)]
+    # the plan's buffers are registered once per plan, not once per call
+    sk, pk = st._test_comms
+    assert len(sk.registered) == 1 and sk.registered[0] is plan.sketch
+    assert len(pk.registered) == 1 and pk.registered[0] is plan.packed
+    assert plan.comm_registered is pk and st.mixed_calls == 3
+
+
+def test_no_collectives_without_communicators(rig):
+    st = rig.make()
+    st.error_dtype = torch.float32
+    _with_comms(rig, st, 1)  # world size 1, no force_exchange, no emulated wire
+    assert rig.call(st) == [("encode_mixed", 0), ("select", 1), ("pack_mixed", 0), ("decode", N.EF14)]
+    assert not st._test_comms[0].registered and not st._test_comms[1].registered
+
+
+def test_pending_deferred_steps_are_finished_first(rig):
+    st = rig.make()
+    st.error_dtype = torch.float32
+    st.defer_decode = True
+    rig.lib.arctopk_exchange_finish = lambda *a: rig.lib.calls.append(("exchange_finish",)) or 0
+    # a default-path call of another bucket (fp32: the option does not apply) that defers its decode
+    G = torch.ones(bucket_numel(SHAPES), dtype=torch.float32)
+    fut = H.group_topk_hook(st, SyntheticBucket(G, SHAPES, index=1, is_last=False))
+    assert not fut.done() and len(st._x_pend) == 1
+    calls = rig.call(st)
+    assert calls == [("exchange_finish",), ("encode_mixed", 0), ("select", 1), ("pack_mixed", 0), ("decode", N.EF14)]
+    assert fut.done() and not st._x_pend
+
+
+def test_bits_at_world_size_two(rig):
+    st = rig.make()
+    st.error_dtype = torch.float32
+    _with_comms(rig, st, 2)
+    rig.call(st)
+    plan = rig.plans[(0, st._plan_ratio())]
+    assert st.comm_bits_this_round == 2 * (2 - 1) * plan.bits_sum == 2000

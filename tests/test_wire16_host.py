@@ -303,3 +303,30 @@ def test_entry_points_refuse_null_arguments_without_a_device():
         assert L.arctopk_decode_wire16(null, p, p, 1, ef, p, p, null) == N.EINVAL
         assert L.arctopk_decode_wire16(null, null, null, 0, ef, null, null, null) == N.EINVAL
     assert not any(buf)
+
+
+# ---- 5. pending deferred steps ---------------------------------------------------------------
+def test_pending_deferred_steps_are_finished_first(rig):
+    st = rig.make()
+    st.wire_dtype = torch.bfloat16
+    st.defer_decode = True
+    rig.lib.arctopk_exchange_finish = lambda *a: rig.lib.calls.append(("exchange_finish",)) or 0
+    # a default-path call of another bucket (bf16: the option does not apply) that defers its decode
+    G = torch.ones(bucket_numel(SHAPES), dtype=BF16)
+    fut = H.group_topk_hook(st, SyntheticBucket(G, SHAPES, index=1, is_last=False))
+    assert not fut.done() and len(st._x_pend) == 1
+    calls = rig.call(st)
+    assert calls == [("exchange_finish",), ("encode", N.EF14, 0), ("select", 1), ("pack_wire16", N.EF14, 0),
+                     ("decode_wire16", N.EF14, 1)]
+    assert fut.done() and not st._x_pend
+
+
+def test_bits_at_world_size_two(rig):
+    st = rig.make(ws=2)
+    st.wire_dtype = torch.bfloat16
+    rig.call(st)
+    plan = next(p for p in rig.plans.values() if p.packed16 is not None)
+    sketch_elems = sum(s.n * plan.r if s.kind == N.SEG_SKETCH else s.n if s.kind == N.SEG_RAW else 0
+                       for s in plan.segments)
+    assert st.comm_bits_this_round == 2 * (2 - 1) * (sketch_elems * 32 + plan.info.values_len * 16)
+    assert st.comm_bits_this_round != 2 * (2 - 1) * plan.bits_sum
