@@ -40,12 +40,26 @@ row / per column of every tensor with the segmented select (arctopk_seg_select):
 
 Ties at the k-th |x| resolve lowest-index first.
 
-Residuals are kept in the bucket's dtype: ``GroupTopKState.error_dtype`` (an fp32 EF14 residual
-under a bf16 bucket) belongs to the ARC-TopK hooks only; these hooks' bf16
-entry points round after every add, as the reference's torch ops do.
+Residuals are kept in the bucket's dtype by default: the bf16 entry points round after every add,
+as the reference's torch ops do.  ``SparseState.error_dtype = torch.float32`` (DESIGN.md section
+4g, not in the reference; environment default ``ARCTOPK_SPARSE_ERROR_DTYPE=fp32``) keeps a bf16
+bucket's ``error_dict[b]`` -- and under EF21 ``global_error_dict[b]`` -- in fp32, as
+``GroupTopKState.error_dtype`` / ``ef21_error_dtype`` do for ARC-TopK.  Such a call runs
+
+    fold    arctopk_sparse_fold_mixed   EF14: E := f(G) + E | EF21: D := f(G) - E (fp32 scratch)
+    select  the fp32 selects above on E / D (TopK's selection is finer than the bf16 path's);
+            RandK's indices are the same draws
+    pack    arctopk_sparse_pack_mixed   values = b(X); EF14: E := X - f(values), the remainder of
+            the rounding, at the selected elements | EF21: E := fma(decay, f(values), E)
+    decode  EF14: the bf16 decode above | EF21: arctopk_sparse_decode_mixed21: fp32 rank-ordered
+            sums, gE := fma(decay, sum / ws, gE), out = b(gE)
+
+with the bf16 wire, the index exchange and the bit accounting of the default path.  The option is
+ignored for fp32 buckets and "noef", and refused with ``large_batch_init`` on a bf16 bucket.
 """
 
 import logging
+import os
 from typing import Dict, List
 
 import torch
@@ -126,6 +140,18 @@ class SparseState(HookState):
         self._ws_bytes: Dict[tuple, int] = {}
         self._seg_geom: Dict[tuple, "_SegGeometry"] = {}  # row / column: per bucket layout and ratio
         self._fold_in = None  # RandK "hash" under EF14: the select applies E (1) or the first-call copy (2)
+        # Residual dtype (not in the reference): None keeps E (and EF21's gE) in
+        # the bucket's dtype; torch.float32 keeps them in fp32 under a bf16 bucket (4 B, under EF21
+        # 8 B, per element of a 2-B bucket, plus EF21's fp32 scratch of the largest bucket), so unsent
+        # mass below 2^-9 of a residual element is carried instead of rounded away.  One option for
+        # both EF modes; ignored for fp32 buckets and noef.
+        env = os.environ.get("ARCTOPK_SPARSE_ERROR_DTYPE", "")
+        if env not in ("", "fp32"):
+            raise ValueError(f"ARCTOPK_SPARSE_ERROR_DTYPE must be 'fp32' (or unset), got {env!r}")
+        self.error_dtype = torch.float32 if env == "fp32" else None
+        self.mixed_calls = 0  # compressed calls that ran with fp32 residuals under a bf16 bucket
+        self._mixed_buckets = set()  # ... and the buckets whose residuals are such
+        self._mixed_scratch = None  # EF21: D = f(G) - E, then the decode's fp32 sums (grown, never shrunk)
 
     # ratio of this call; the c4 variant overrides (gradual compression)
     def _call_ratio(self) -> float:
@@ -133,6 +159,42 @@ class SparseState(HookState):
 
     def _on_compression_start(self):
         pass
+
+    def _mixed_residual(self, bucket_dtype, ef: int) -> bool:
+        """Whether this call keeps fp32 residuals under a bf16 bucket.  ValueError for an
+        ``error_dtype`` other than None / torch.float32; ignored for fp32 buckets and without
+        error feedback."""
+        ed = self.error_dtype
+        if ed is not None and ed is not torch.float32:
+            raise ValueError(f"error_dtype must be None or torch.float32, got {ed!r}")
+        return ed is not None and bucket_dtype == torch.bfloat16 and ef != N.EF_NONE
+
+    def state_dict(self) -> dict:
+        out = super().state_dict()
+        # the residual dtype option, and the buckets whose fp32 residuals belong to a bf16 bucket
+        out["error_dtype"] = "fp32" if self.error_dtype is torch.float32 else None
+        out["mixed_buckets"] = sorted(self._mixed_buckets)
+        return out
+
+    def load_state_dict(self, sd: dict, device=None) -> None:
+        """As HookState.load_state_dict.  A checkpoint written with ``error_dtype=torch.float32``
+        (fp32 residuals of bf16 buckets) loads only into a state that has the option set: ValueError
+        otherwise, since rounding those residuals to bf16 would drop what they exist to carry.  The
+        other way round -- bf16 residuals into a state with the option -- converts them to fp32,
+        which is exact."""
+        mixed = [int(b) for b in sd.get("mixed_buckets", ())]
+        if mixed and self.error_dtype is not torch.float32:
+            raise ValueError(f"the checkpoint holds float32 residuals of bfloat16 buckets {mixed} "
+                             "(error_dtype=torch.float32): set error_dtype=torch.float32 on this state "
+                             "before loading it")
+        super().load_state_dict(sd, device)
+        self._mixed_buckets = set(mixed)
+        if self.error_dtype is torch.float32 and self.use_error_feedback != "noef":
+            for table in (self.error_dict, self.global_error_dict):
+                for b, t in table.items():
+                    if t.dtype == torch.bfloat16:
+                        table[b] = t.float()
+                        self._mixed_buckets.add(int(b))
 
 
 def _workspace(state, device, numels) -> torch.Tensor:
@@ -215,6 +277,9 @@ def _sparse_hook_impl(state: SparseState, bucket, c4: bool = False) -> "torch.fu
         # (sparse_hook.py:172-175, sparse_hook_c4.py:201-204)
         if state.iter < state.start_compress_iter:
             logger.info("Using large batch initialization in EF21!!")
+        if state._mixed_residual(bucket.buffer().dtype, N.EF21):
+            raise ValueError("error_dtype=torch.float32 does not run with large_batch_init: that hook "
+                             "keeps a bfloat16 bucket's residuals in bfloat16")
         return _large_batch_ef21(state, bucket, c4)
     state.maybe_accumulate_momentum_on_bucket(bucket)
     group = state.process_group if state.process_group is not None else dist.group.WORLD
@@ -237,6 +302,9 @@ def _sparse_hook_impl(state: SparseState, bucket, c4: bool = False) -> "torch.fu
     dt = N.DTYPE_CODE[dtype]
     # EF21 residual scaling: E += error_decay * C(D), gE += error_decay * out (:265, :296)
     decay = float(state.error_decay)
+
+    if state._mixed_residual(dtype, ef):  # fp32 residuals under this bf16 bucket (error_dtype)
+        return _mixed_call(state, bucket, group, world_size, ef, decay)
 
     if ef == N.EF14:
         err_in = b in state.error_dict
@@ -298,6 +366,150 @@ def _check_compressible(state: SparseState, input_tensor: torch.Tensor) -> None:
         raise RuntimeError("sparse HIP codec needs a float32 or bfloat16 bucket on a GPU")
 
 
+def _bucket_layout(state: SparseState, input_tensor, tensors, ratio: float):
+    """(row / column geometry or None, numels, ks, element offsets, k offsets, sum of ks) of a
+    bucket's tensors at this call's ratio."""
+    numels = [t.numel() for t in tensors]
+    # row / column: per-segment selection; ks are then the per-tensor totals
+    seg = _seg_geometry(state, tensors, ratio) if state.sparse_type != "tensor" else None
+    ks = seg.ks if seg is not None else [max(1, int(n * ratio)) for n in numels]
+    offsets: List[int] = []
+    off = 0
+    for t in tensors:
+        if (t.data_ptr() - input_tensor.data_ptr()) // input_tensor.element_size() != off:
+            raise RuntimeError("bucket gradient views must tile the buffer in order")
+        offsets.append(off)
+        off += t.numel()
+    k_off: List[int] = []
+    acc = 0
+    for k in ks:
+        k_off.append(acc)
+        acc += k
+    return seg, numels, ks, offsets, k_off, acc
+
+
+def _mixed_call(state: SparseState, bucket, group, world_size: int, ef: int,
+                decay: float) -> "torch.futures.Future[torch.Tensor]":
+    """A compressed call of a bf16 bucket whose residuals are fp32 (``error_dtype``, DESIGN.md
+    section 4g), on the caller's stream: fold, the fp32 select (or RandK's draw), pack, the bf16
+    exchange of the default path, decode.  EF21's first call of a bucket is the dense one, as in
+    the default path, with E_0 = f(G) and gE_0 = f(out)."""
+    L = N.lib()
+    input_tensor = bucket.buffer()
+    tensors = bucket.gradients()
+    device = input_tensor.device
+    b = bucket.index()
+    total = input_tensor.shape[0]
+    stream = torch.cuda.current_stream(device).cuda_stream
+    x = input_tensor.data_ptr()
+    f32 = torch.float32
+
+    if ef == N.EF21 and b not in state.error_dict:  # (:213-226)
+        logger.info("A tensor of length %s that represents local/global error is created.", total)
+        state.error_dict[b] = input_tensor.float()
+        dist.all_reduce(input_tensor, group=group, async_op=False)
+        input_tensor.div_(world_size)
+        state.global_error_dict[b] = input_tensor.float()
+        state._mixed_buckets.add(int(b))
+        state.maybe_increase_iter(bucket)
+        fut = torch.futures.Future()
+        fut.set_result(input_tensor)
+        return fut
+
+    err_in = b in state.error_dict
+    if not err_in:  # EF14's first call: the fold writes every element
+        logger.info("A zero tensor of length %s that represents local error is created.", total)
+        state.error_dict[b] = torch.empty(total, device=device, dtype=f32)
+        state._mixed_buckets.add(int(b))
+    err = _residual_on(state.error_dict, b, input_tensor, "error_dict", f32)
+    gerr = scratch = None
+    if ef == N.EF21:
+        gerr = _residual_on(state.global_error_dict, b, input_tensor, "global_error_dict", f32)
+        scratch = state._mixed_scratch
+        if scratch is None or scratch.device != device or scratch.numel() < total:
+            scratch = state._mixed_scratch = torch.empty(total, dtype=f32, device=device)
+    # EF14: X = f(G) + E lives in E; EF21: D = f(G) - E lives in the scratch
+    src = err if ef == N.EF14 else scratch
+    N.check(L.arctopk_sparse_fold_mixed(x, err.data_ptr(), N.ptr(scratch), total, ef, int(err_in), stream),
+            "arctopk_sparse_fold_mixed")
+
+    seed = None
+    if state.random:  # shared reseed so every rank draws the same indices (:230-235)
+        seed = torch.randint(0, 1_000_000_000, (1,), generator=state.rng).item()
+        torch.manual_seed(seed)
+    seg, numels, ks, offsets, k_off, sum_k = _bucket_layout(state, input_tensor, tensors, state._call_ratio())
+    nt = len(tensors)
+    a_off, a_n, a_k, a_ko = (N.i64_array(offsets), N.i64_array(numels), N.i64_array(ks), N.i64_array(k_off))
+    values = torch.empty(sum_k, dtype=torch.bfloat16, device=device)
+    indices = torch.empty(sum_k, dtype=torch.int32, device=device)
+    hashed = state.random and state.index_source == "hash"
+    if state.random and not hashed:  # the reference's own draws, as in the default path
+        if seg is not None:
+            indices.copy_(_seg_reference_draws(seg, device if state.index_source == "torch" else None))
+        elif state.index_source == "torch":
+            for t, k, ko in zip(tensors, ks, k_off):
+                indices[ko:ko + k].copy_(torch.randperm(t.numel(), device=device)[:k])
+        else:
+            host = torch.empty(sum_k, dtype=torch.int32)
+            for t, k, ko in zip(tensors, ks, k_off):
+                host[ko:ko + k].copy_(torch.randperm(t.numel())[:k])
+            indices.copy_(host)
+    elif seg is not None:  # the selects' own fp32 gather goes unused: the pack rounds from src
+        ws = state._workspace
+        if ws is None or ws.device != device or ws.numel() < seg.ws_bytes:
+            ws = state._workspace = torch.empty(seg.ws_bytes, dtype=torch.uint8, device=device)
+        sel_vals = torch.empty(sum_k, dtype=f32, device=device)
+        N.check(L.arctopk_seg_select(src.data_ptr(), nt, a_off, seg.a_rows, seg.a_cols, seg.a_kseg, a_ko,
+                                     int(seg.by_column), int(hashed), int(seed) if hashed else 0,
+                                     indices.data_ptr(), sel_vals.data_ptr(), ws.data_ptr(), N.F32, 0, stream),
+                "arctopk_seg_select")
+    elif hashed:  # indices only: the keys never read the data
+        ws_buf = _workspace(state, device, numels)
+        N.check(L.arctopk_randk_select(None, nt, None, a_n, a_k, a_ko, int(seed), indices.data_ptr(), None,
+                                       ws_buf.data_ptr(), N.F32, 0, stream), "arctopk_randk_select")
+    else:
+        ws_buf = _workspace(state, device, numels)
+        sel_vals = torch.empty(sum_k, dtype=f32, device=device)
+        N.check(L.arctopk_topk_select(src.data_ptr(), nt, a_off, a_n, a_k, a_ko, indices.data_ptr(),
+                                      sel_vals.data_ptr(), ws_buf.data_ptr(), N.F32, 0, stream),
+                "arctopk_topk_select")
+    state.last_indices, state.last_k = indices, ks
+    N.check(L.arctopk_sparse_pack_mixed(src.data_ptr(), err.data_ptr(), total, nt, a_off, a_k, a_ko,
+                                        indices.data_ptr(), values.data_ptr(), ef, decay, stream),
+            "arctopk_sparse_pack_mixed")
+
+    # the exchange of the default path: the values are bf16, the indices int32
+    bits_sum = sum_k * (dtype_bits(torch.bfloat16) + (0 if state.random else 32))
+    if state.random:
+        state.comm_bits_this_round += 2 * (world_size - 1) * bits_sum
+        if world_size > 1:
+            dist.all_reduce(values, group=group, async_op=False)
+        all_vals, all_idx, nranks = values, indices, 1
+        accumulate = 2 if hashed and not (seg is not None and seg.by_column) else 0
+    else:
+        state.comm_bits_this_round += (world_size - 1) * world_size * bits_sum
+        all_vals, all_idx, nranks = values, indices, world_size
+        if world_size > 1:
+            all_vals = torch.empty(world_size * sum_k, dtype=torch.bfloat16, device=device)
+            all_idx = torch.empty(world_size * sum_k, dtype=torch.int32, device=device)
+            _all_gather_flat(all_vals, values, group, world_size)
+            _all_gather_flat(all_idx, indices, group, world_size)
+        accumulate = 3 if seg is not None and seg.by_column else 1
+    if ef == N.EF14:
+        N.check(L.arctopk_sparse_decode(x, total, nt, a_off, a_k, a_ko, sum_k, all_idx.data_ptr(),
+                                        all_vals.data_ptr(), nranks, world_size, accumulate, None, decay,
+                                        N.BF16, stream), "arctopk_sparse_decode")
+    else:  # the fold's scratch is free again: it takes the fp32 sums
+        N.check(L.arctopk_sparse_decode_mixed21(x, gerr.data_ptr(), scratch.data_ptr(), total, nt, a_off, a_k,
+                                                a_ko, sum_k, all_idx.data_ptr(), all_vals.data_ptr(), nranks,
+                                                world_size, decay, stream), "arctopk_sparse_decode_mixed21")
+    state.mixed_calls += 1
+    state.maybe_increase_iter(bucket)
+    fut = torch.futures.Future()
+    fut.set_result(input_tensor)
+    return fut
+
+
 def _compress_exchange(state: SparseState, bucket, group, world_size: int, ef: int, ratio: float,
                        seed, e_decay: float, g_decay: float, count_bits: bool, on_values=None,
                        ef14_folded: bool = False) -> None:
@@ -318,23 +530,7 @@ def _compress_exchange(state: SparseState, bucket, group, world_size: int, ef: i
     total = input_tensor.shape[0]
     stream = torch.cuda.current_stream(device).cuda_stream
     dt = N.DTYPE_CODE[dtype]
-    numels = [t.numel() for t in tensors]
-    # row / column: per-segment selection; ks are then the per-tensor totals
-    seg = _seg_geometry(state, tensors, ratio) if state.sparse_type != "tensor" else None
-    ks = seg.ks if seg is not None else [max(1, int(n * ratio)) for n in numels]
-    offsets: List[int] = []
-    off = 0
-    for t in tensors:
-        if (t.data_ptr() - input_tensor.data_ptr()) // input_tensor.element_size() != off:
-            raise RuntimeError("bucket gradient views must tile the buffer in order")
-        offsets.append(off)
-        off += t.numel()
-    k_off: List[int] = []
-    acc = 0
-    for k in ks:
-        k_off.append(acc)
-        acc += k
-    sum_k = acc
+    seg, numels, ks, offsets, k_off, sum_k = _bucket_layout(state, input_tensor, tensors, ratio)
     nt = len(tensors)
     fold14 = ef == N.EF14  # the pre-compression bucket lives in E (arctopk_ef14_fold)
     a_off, a_n, a_k, a_ko = (N.i64_array(offsets), N.i64_array(numels), N.i64_array(ks),

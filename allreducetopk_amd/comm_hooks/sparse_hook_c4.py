@@ -7,8 +7,9 @@ Differences from ``sparse_hook`` (reference sparse_hook_c4.py:140-151, :175-189,
 down to ``compress_ratio`` over ``start_compress_iter + warmup_iters`` iterations
 after compression starts, and ``cal_k`` takes ``(state, tensor)``.
 
-As in ``sparse_hook``, residuals stay in the bucket's dtype: the ARC-TopK hooks' ``error_dtype``
-option (fp32 EF14 residuals under a bf16 bucket) is not offered here.
+As in ``sparse_hook``, ``SparseState.error_dtype = torch.float32`` (or
+``ARCTOPK_SPARSE_ERROR_DTYPE=fp32``) keeps a bf16 bucket's EF14 / EF21 residuals in fp32 (DESIGN.md
+section 4g); the ramp runs with it, every call selecting at that call's ratio.
 """
 
 import logging

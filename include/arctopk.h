@@ -593,6 +593,67 @@ int arctopk_ef_apply(void* x, void* E, int64_t numel, int32_t ef, int32_t err_in
 int arctopk_ef14_fold(const void* x, void* E, int64_t numel, int32_t err_in, int32_t dtype,
                       void* stream);
 
+/* ---- TopK / RandK baselines: fp32 residuals under a bf16 bucket (SparseState.error_dtype) ---- */
+/*
+ * In this section bucket-typed buffers (g, vals, out) are bf16 and residual buffers (E, D, gE,
+ * scratch) are fp32, whatever the names' meaning elsewhere.  f = bf16 -> fp32 (exact), b = fp32 ->
+ * bf16 (round to nearest even, NaN -> 0x7FC0).  Indices come from the existing selects run on the
+ * fp32 buffer with dtype = ARCTOPK_F32 and zero_selected = 0 (arctopk_topk_select,
+ * arctopk_seg_select, arctopk_randk_select); the values leave as bf16, so the exchange and EF14's
+ * decode (arctopk_sparse_decode, dtype = ARCTOPK_BF16) are the bf16 path's.  Tensor i's extent is
+ * offsets[i + 1] - offsets[i] (the last one's ends at numel): the tensors tile the bucket in order.
+ */
+
+/*
+ * EF pre-apply of a whole bucket into the fp32 buffers, one pass; g is not written:
+ *   EF14 : E := f(g) + E (err_in = 1; one fp32 add) or E := f(g) (first call; E is not read); D unused
+ *   EF21 : D := f(g) - E (one fp32 subtract); E is not written
+ * g, E and D 16-B aligned: 16 B of g and 2 x 16 B of fp32 in and out per unit of 8 elements,
+ * nontemporal, several units' loads in flight before the first store, and the last numel % 8
+ * elements one by one; otherwise element by element.  ARCTOPK_EINVAL for a null g or E (EF21: D), an
+ * ef other than EF14 / EF21 or a pointer not aligned to its element.
+ * Replaces: input_tensor.add_(E, alpha=+-1) (sparse_hook.py:205, :212) and EF14's full-bucket
+ * E.copy_(input_tensor) (:258), as arctopk_ef14_fold / arctopk_ef_apply do for one dtype.
+ */
+int arctopk_sparse_fold_mixed(const void* g, void* E, void* D, int64_t numel, int32_t ef,
+                              int32_t err_in, void* stream);
+
+/*
+ * Gather and residual at the selected elements: for tensor i and j < ks[i], with
+ * e = offsets[i] + idx[k_off[i] + j],
+ *   vals[k_off[i] + j] = b(src[e])
+ *   EF14 (src == E, after the fold): E[e] := src[e] - f(vals)   (exact: what the bf16 wire drops)
+ *   EF21 (src == D)                : E[e] := fma(decay, f(vals), E[e])   (one rounding)
+ * Other elements of E are untouched.  Every index is checked against its tensor's extent: one
+ * outside it writes vals = 0 and nothing else.  One launch per ARCTOPK_SPARSE_MAX_BATCH tensors;
+ * ARCTOPK_EINVAL, with nothing enqueued, for null arrays, tensors that do not tile [offsets[0],
+ * numel) in order, a k outside [1, extent], EF14 with src != E, or an ef other than EF14 / EF21.
+ * Replaces: tensor[indices] (sparse_hook.py:22, :28), `tensor[indices] = 0` (:104) and
+ * E.add_(C(G - E), alpha=error_decay) (:265) -- arctopk_sparse_gather + arctopk_sparse_residual.
+ */
+int arctopk_sparse_pack_mixed(const void* src, void* E, int64_t numel, int32_t ntensors,
+                              const int64_t* offsets, const int64_t* ks, const int64_t* k_off,
+                              const int32_t* idx, void* vals, int32_t ef, float decay, void* stream);
+
+/*
+ * EF21 decode: scratch (numel fp32) := 0, then for rank q = 0..nranks-1 in order
+ * scratch[off + idx_q[j]] += f(vals_q[j]) (indices within a payload are distinct; checked against
+ * the tensor's extent, one outside it is skipped); then on every element
+ *   m = scratch / world_size (correctly rounded: x 1/ws for a power of two, else a division)
+ *   gE := fma(decay, m, gE);  out = b(gE)
+ * (m = 0 where nothing was selected: gE keeps its bits except a stored -0.0, as gE + 0.0 does).
+ * RandK passes its all-reduced payload with nranks = 1.  `vals` / `idx` hold nranks consecutive
+ * payloads of packed_len entries.  out, gE and scratch 16-B aligned: units of 8 elements as the
+ * fold's; otherwise element by element.
+ * Replaces: the scatter(-add) / ws of sparse_hook.py:273-292 and gE.add_(out, alpha=error_decay);
+ * out = gE (:295-297) -- arctopk_sparse_decode with gerr, without its roundings to bf16.
+ */
+int arctopk_sparse_decode_mixed21(void* out, void* gE, void* scratch, int64_t numel,
+                                  int32_t ntensors, const int64_t* offsets, const int64_t* ks,
+                                  const int64_t* k_off, int64_t packed_len, const int32_t* idx,
+                                  const void* vals, int32_t nranks, int32_t world_size, float decay,
+                                  void* stream);
+
 /*
  * Momentum fold of a whole bucket, in place, stream-ordered, one launch per
  * ARCTOPK_SPARSE_MAX_BATCH tensors: for every tensor i,
