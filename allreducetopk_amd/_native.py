@@ -110,6 +110,10 @@ _SIGS = {
                                       c_void_p, c_void_p]),
     "arctopk_decode_wire16": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
                                         c_void_p]),
+    "arctopk_decode_wire16_scatter": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
+                                                c_void_p]),
+    "arctopk_plan_bind_wire16": (c_int32, [c_void_p, c_void_p]),
+    "arctopk_diag_wire16_scatters": (c_int32, [c_void_p, ctypes.POINTER(c_int64)]),
     "arctopk_pack_segments": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32,
                                         c_void_p, c_void_p, c_void_p, c_void_p]),
     "arctopk_decode_segments": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32,

@@ -181,6 +181,7 @@ class BucketPlan:
         # on that branch, and the packed communicator it is registered with
         self.packed16 = None
         self.packed16_registered = None
+        self.wire16_bound = False  # arctopk_plan_bind_wire16(packed16) holds: its exchange steps use the bf16 wire
         # the device generator's Philox offset after the reference's per-tensor
         # torch.randn(m, r, device=...) draws of one call (see _reseed_global)
         adv = N.c_uint64()
@@ -598,6 +599,26 @@ class GroupTopKState(HookState):
             raise ValueError(f"ARCTOPK_WIRE_DTYPE must be 'bf16' (or unset), got {env!r}")
         self.wire_dtype = torch.bfloat16 if env == "bf16" else None
         self.wire16_calls = 0  # compressed calls of fp32 buckets whose packed values went out as bf16
+        # Where a bf16-wire bucket's call runs (section 4f): "inline" is the phase-by-phase call above;
+        # "step" sends it through the one-native-call exchange step (arctopk_exchange_step on a plan
+        # bound with arctopk_plan_bind_wire16), so its halved packed all-reduce runs on the exchange
+        # stream under the next bucket's encode, its decode is deferred and its Future is an
+        # ExchangeFuture like the default path's.  Such a bucket runs whole: no exchange groups, no
+        # select stream, no trailing step and no zero-rows encode.  No effect where _wire16() is
+        # false.  Environment default: ARCTOPK_WIRE_EXCHANGE=step.
+        env = os.environ.get("ARCTOPK_WIRE_EXCHANGE", "")
+        if env not in ("", "step"):
+            raise ValueError(f"ARCTOPK_WIRE_EXCHANGE must be 'step' (or unset), got {env!r}")
+        self.wire_exchange = "step" if env == "step" else "inline"
+        self.wire16_step_calls = 0  # ... those of them that went through the exchange step
+
+    def _wire16_step(self, wire16: bool) -> bool:
+        """Whether a bf16-wire call (`wire16`: what _wire16 returned) goes through the exchange step.
+        ValueError for a ``wire_exchange`` other than "inline" / "step"."""
+        we = self.wire_exchange
+        if not isinstance(we, str) or we not in ("inline", "step"):
+            raise ValueError(f"wire_exchange must be 'inline' or 'step', got {we!r}")
+        return wire16 and we == "step"
 
     def _wire16(self, bucket_dtype) -> bool:
         """Whether this call sends an fp32 bucket's packed values as bf16.  ValueError for a
@@ -774,6 +795,7 @@ class GroupTopKState(HookState):
         # for information: the residuals of an fp32 bucket are fp32 either way, so a checkpoint loads
         # under either setting
         out["wire_dtype"] = "bf16" if self.wire_dtype is torch.bfloat16 else None
+        out["wire_exchange"] = self.wire_exchange  # (where the call runs: the residuals do not depend on it)
         return out
 
     def load_state_dict(self, sd: dict, device=None) -> None:
@@ -1413,6 +1435,7 @@ def group_topk_hook(state: GroupTopKState, bucket: dist.GradBucket
     mixed = state._mixed_residual(input_tensor.dtype, ef)
     # an fp32 bucket whose packed values travel as bf16 (state.wire_dtype)
     wire16 = state._wire16(input_tensor.dtype)
+    w16step = state._wire16_step(wire16)  # ... through the exchange step (state.wire_exchange)
     if ef == N.EF14:
         if b not in state.error_dict:
             logger.info("A zero tensor of length %s that represents local error is created.", total)
@@ -1462,7 +1485,7 @@ def group_topk_hook(state: GroupTopKState, bucket: dist.GradBucket
     L = _LIB[0]
     # EF14: may this call skip the rows its previous call zeroed?  (consumes the bucket's record)
     zr = state._zr_take(b, plan, err, ef)
-    path = _FP32_EF21 if mixed21 else _FP32_EF14 if mixed else _WIRE16 if wire16 else None
+    path = _FP32_EF21 if mixed21 else _FP32_EF14 if mixed else _WIRE16 if (wire16 and not w16step) else None
     if path is not None:
         return _phased_call(path, state, bucket, input_tensor, plan, ef, err, gerr, err_in, seed, group, world_size, sid)
     if not state.host_staged:
@@ -1470,10 +1493,16 @@ def group_topk_hook(state: GroupTopKState, bucket: dist.GradBucket
         # world size > 1 (or with force_exchange: the N > 1 code path over one-rank
         # communicators), and earlier buckets' deferred decodes
         comms = world_size > 1 or state.force_exchange or state.emulate_wire is not None
+        if w16step:
+            # the step on the bf16 wire: the plan is bound to its bf16 packed buffer below; no zero rows
+            # (a selected row of E holds its rounding remainder), groups, select stream or trailing step
+            zr = False
+            if plan.packed16 is None:  # zero-filled: the alignment pads ride the all-reduce as zeros
+                plan.packed16 = torch.zeros(max(1, plan.info.packed_len), dtype=torch.bfloat16, device=dev)
         sk = pk = None
         if comms:
             sk, pk = state._exchange_comms(group, dev)  # (a failed communicator: the step returns its status)
-            _register_comm_buffers(plan, sk, pk)
+            _register_comm_buffers(plan, sk, pk, w16step)
         vslot, V, draw = _call_projections(state, plan, bucket, seed, sid, dev, dtype)
         # device V is drawn by the step itself (`draw`), the predicted next call's by its select
         vptr = None if V is None else V.data_ptr()
@@ -1502,7 +1531,7 @@ def group_topk_hook(state: GroupTopKState, bucket: dist.GradBucket
         sel_backward = state.select_streams == "on" or (
             state.select_streams == "auto" and state._sel_small_last >= state.select_stream_min_buckets)
         if (not comms and defer and marks is None and device_v and state.trail_bytes > 0
-                and ef != N.EF21 and state._trail is None and not sel_backward
+                and ef != N.EF21 and state._trail is None and not sel_backward and not w16step
                 and total * input_tensor.element_size() <= state.trail_bytes):
             rc = L.arctopk_exchange_trail(plan.handle, input_tensor.data_ptr(), N.ptr(err), N.ptr(gerr), ef,
                                           int(err_in), int(draw), seed, None, sid)
@@ -1520,14 +1549,14 @@ def group_topk_hook(state: GroupTopKState, bucket: dist.GradBucket
             if rc != N.EINVAL:
                 N.check(rc, "arctopk_exchange_trail")
         trail = state._trail
-        if trail is not None and (trail[4] != sid or trail[0] is plan):
-            state.flush_exchange()  # another stream, or the same bucket again: enqueued on its own
+        if trail is not None and (trail[4] != sid or trail[0] is plan or w16step):
+            state.flush_exchange()  # another stream, the same bucket again, a bf16-wire step: enqueued on its own
             trail = None
         if trail is not None:  # not a ride candidate of this call: carried (or enqueued) by it
             pend.remove(trail)
             state._trail = None
         units = None
-        if (comms and state.async_exchange and marks is None and state.exchange_groups != "off"
+        if (comms and state.async_exchange and marks is None and state.exchange_groups != "off" and not w16step
                 and (state.exchange_groups == "all" or not pend or bucket.is_last())):
             units = plan.groups(state.group_bytes)
         grouped = units is not None
@@ -1537,6 +1566,12 @@ def group_topk_hook(state: GroupTopKState, bucket: dist.GradBucket
         # pending step (its decode is enqueued on that step's own stream)
         if any(_bucket_plan_of(e_[0]) is plan or e_[4] != sid for e_ in pend):
             state.flush_exchange()
+        # the plan's exchange steps run on the bf16 wire while it is bound to its bf16 buffer (nothing
+        # of the plan is pending here: a binding changes between a plan's steps only)
+        if w16step != getattr(plan, "wire16_bound", False):
+            N.check(L.arctopk_plan_bind_wire16(plan.handle, plan.packed16.data_ptr() if w16step else None),
+                    "arctopk_plan_bind_wire16")
+            plan.wire16_bound = w16step
         ars = None
         if comms:
             ars = state._side_stream(state._ar_streams, dev, XSTREAM_PRIORITY)
@@ -1548,7 +1583,7 @@ def group_topk_hook(state: GroupTopKState, bucket: dist.GradBucket
         if bucket.is_last():
             state._sel_small_last, state._sel_small = state._sel_small, 0
         side = None
-        if (state.select_streams != "off" and not grouped and marks is None and dd
+        if (state.select_streams != "off" and not grouped and marks is None and dd and not w16step
                 and (not comms or ars is not None)
                 and (state.select_streams == "on"
                      or (small and state._sel_small_last >= state.select_stream_min_buckets))):
@@ -1625,10 +1660,13 @@ def group_topk_hook(state: GroupTopKState, bucket: dist.GradBucket
             nplan.v_drawn, nplan.v_stream = nseed, sid
         if vslot >= 0:
             plan.projection_consumed(vslot, torch.cuda.current_stream(dev))
-        if ef == N.EF14 and not grouped:
+        if ef == N.EF14 and not grouped and not w16step:
             state._zr_note(b, plan, err)
         _ht("native_step")
-        state.comm_bits_this_round += 2 * (world_size - 1) * plan.bits_sum  # (:278)
+        if w16step:
+            state.wire16_step_calls += 1
+        state.comm_bits_this_round += 2 * (world_size - 1) * (
+            _count_wire16(state, b, plan) if w16step else plan.bits_sum)  # (:278)
         state.maybe_increase_iter(bucket)
         if not defer:
             fut.set_result(input_tensor)

@@ -470,6 +470,11 @@ struct arctopk_plan {
                                         //   the plan's first arctopk_encode_mixed / arctopk_pack_mixed
     void* w16;                          // work tables of the bf16-wire pack and decode of an fp32 plan
                                         //   (wire16.hip), built by the plan's first call there
+    void* b_packed16;                   // bound by arctopk_plan_bind_wire16: the plan's exchange steps
+                                        //   send their packed values through it as bf16 (NULL: b_packed)
+    int x_w16;                          // the deferred step is such a one (beside x_ef / x_ws): its
+                                        //   decode is arctopk_decode_wire16 of b_packed16
+    int64_t w16_scatters;               // steps whose decode was the zero-ahead scatter (diagnostics)
 };
 namespace arctopk {
 // frees a plan's fp32-residual work tables (arctopk_plan_destroy)
@@ -479,6 +484,14 @@ void mixed_forget(arctopk_plan* p);
 bool mixed_tile_counts(const arctopk_plan* p, int64_t* vlds, int64_t* vglobal);
 // ... and its bf16-wire work tables
 void wire16_forget(arctopk_plan* p);
+// the bf16-wire pack and decode of the exchange step (wire16.hip): arctopk_pack_wire16 whose kernel
+// completes `done` (not null), and arctopk_decode_wire16 -- `scatter`: into a bucket already zero,
+// arctopk_decode_wire16_scatter -- whose kernel completes `done` when given one; an empty work
+// table records the event instead
+int pack_wire16_signal(const arctopk_plan* p, const void* grad, void* err, int32_t ef, int32_t err_in,
+                       const int32_t* rowlist, const int32_t* slotmap, void* packed, void* stream, void* done);
+int decode_wire16_signal(const arctopk_plan* p, const void* packed, const int32_t* rowlist, const int32_t* slotmap,
+                         int32_t ws, int32_t ef, void* gerr, void* out, bool scatter, void* stream, void* done);
 // host bookkeeping of the plan, like the exchange step's x_* fields
 inline void zr_clear(const arctopk_plan* p) {
     if (p) const_cast<arctopk_plan*>(p)->zr_valid = 0;

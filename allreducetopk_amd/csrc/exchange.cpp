@@ -14,6 +14,10 @@
 // bucket of a backward runs inline (its all-reduce and decode on the caller's stream, after
 // the previous bucket's decode): nothing is left in flight when the hook returns for it.
 //
+// A plan bound to a bf16 packed buffer (arctopk_plan_bind_wire16, wire16.hip) runs the same step with
+// its packed values on the wire as bf16: its pack, packed all-reduce and decode differ, the streams,
+// events, deferral and watchdog are the ones above.
+//
 // Collectives go through an arctopk_comm: an RCCL communicator this library owns (RCCL is
 // resolved at run time from the library torch itself loaded, so the process holds one RCCL),
 // or a caller-supplied callback (tests drive the same orchestration over gloo).
@@ -575,6 +579,27 @@ int wait_ar(arctopk_plan* p, hipStream_t st) {
 }  // namespace
 
 namespace {
+// The decode of plan p's step -- deferred (x_ef, x_ws, x_gerr, x_bucket) or the running one's, whose
+// values the caller passes -- on `st`; `done` (may be null) completed by the kernel.  A bf16-wire
+// step (w16) decodes its bound bf16 buffer: the zero-ahead scatter when the step zeroed the bucket
+// (x_fin 3), else the whole decode; never the fused finalize, never in another plan's launch.
+int decode_step(arctopk_plan* p, bool w16, int32_t ws, int32_t ef, void* gerr, void* bucket, hipStream_t st,
+                void* done) {
+    if (!w16) return arctopk::decode_signal(p, p->b_packed, p->b_slotmap, ws, ef, gerr, bucket, st, done);
+    const bool scatter = p->x_fin == 3;
+    const int e = arctopk::decode_wire16_signal(p, p->b_packed16, p->b_rowlist, p->b_slotmap, ws, ef, gerr, bucket,
+                                                scatter, st, done);
+    if (!e && scatter) ++p->w16_scatters;
+    return e;
+}
+// the plan's deferred step is decoded (or about to be recorded anew)
+inline void x_clear(arctopk_plan* p) {
+    p->x_deferred = p->x_fin = p->x_w16 = 0;
+    p->x_stream = nullptr;
+}
+}  // namespace
+
+namespace {
 // a deferred pack (world size 1) that no encode launch took: its own launch
 int pack_now(arctopk_plan* p, void* stream) {
     if (!p->x_pack) return 0;
@@ -617,6 +642,7 @@ int trail_run(arctopk_plan* c, hipStream_t st) {
     c->x_gerr = c->x_t_gerr;
     c->x_ef = c->x_t_ef;
     c->x_ws = 1;
+    c->x_w16 = 0;
     c->x_stream = nullptr;
     return 0;
 }
@@ -662,13 +688,10 @@ extern "C" int arctopk_exchange_finish(arctopk_plan* p, void* stream, void* cons
     int e = pack_now(p, st);
     if (!e) e = wait_ar(p, st);
     if (!e) e = mark(marks, ARCTOPK_MARK_PACKED_AR, st);
-    if (!e) e = arctopk::decode_signal(p, p->b_packed, p->b_slotmap, p->x_ws, p->x_ef, p->x_gerr, p->x_bucket, st, nullptr);
+    if (!e) e = decode_step(p, p->x_w16 != 0, p->x_ws, p->x_ef, p->x_gerr, p->x_bucket, st, nullptr);
     if (!e) e = mark(marks, ARCTOPK_MARK_DECODE, st);
     if (!e) e = join_stream(p, st, cs);
-    if (!e) {
-        p->x_deferred = p->x_fin = 0;
-        p->x_stream = nullptr;
-    }
+    if (!e) x_clear(p);
     return e;
 }
 
@@ -720,6 +743,16 @@ int exchange_step(arctopk_plan* p, void* bucket, void* err, void* gerr, int32_t 
     // deferring with a collective needs the all-reduce stream (the decode waits for its event)
     if (defer && packed_comm && (!ar_stream || ar_stream == stream)) return ARCTOPK_EINVAL;
     if (ride && (ride == p || !ride->x_deferred)) return ARCTOPK_EINVAL;
+    // A plan bound to a bf16 packed buffer (arctopk_plan_bind_wire16) runs the step on the bf16 wire:
+    // the pack, the packed all-reduce and the decode differ, the rest is the default step's.  It has
+    // no zero-rows encode (a selected row of E keeps its remainder), no select stream and carries
+    // no trailing step, and its kernels take 16-B aligned bucket and residuals.
+    const bool w16 = p->b_packed16 != nullptr;
+    if (w16 && (p->dtype != ARCTOPK_F32 || (err_in != ARCTOPK_ERR_IN_NONE && err_in != ARCTOPK_ERR_IN_READ) ||
+                (sel_stream && sel_stream != stream) || (ef != ARCTOPK_EF_NONE && !err) ||
+                (ef == ARCTOPK_EF21 && !gerr) || (((uintptr_t)bucket | (uintptr_t)err | (uintptr_t)gerr) & 15)))
+        return ARCTOPK_EINVAL;
+    if (trail && trail->b_packed16) return ARCTOPK_EINVAL;  // (a trailing step's decode is the fused finalize)
     // a communicator that failed (watchdog timeout, RCCL error, abort) takes no more work
     if (int f = comm_failed(sketch_comm)) return f;
     if (int f = comm_failed(packed_comm)) return f;
@@ -735,7 +768,7 @@ int exchange_step(arctopk_plan* p, void* bucket, void* err, void* gerr, int32_t 
     arctopk_plan* carry = nullptr;
     if (!e && trail) {
         constexpr int64_t big_rows = ARCTOPK_SEL_BIG_ROWS;
-        const bool fits = !sketch_comm && !marks && trail->device == p->device && trail->dtype == p->dtype &&
+        const bool fits = !w16 && !sketch_comm && !marks && trail->device == p->device && trail->dtype == p->dtype &&
                           trail->r == p->r && p->r == 4 && trail->x_t_ef == ef && !trail->x_t_err_in == !err_in &&
                           ef != ARCTOPK_EF21 && p->n_large_batches > 0 && p->n_split == 0 &&
                           trail->n_large_batches == 0 && trail->n_small > 0 &&
@@ -823,21 +856,20 @@ int exchange_step(arctopk_plan* p, void* bucket, void* err, void* gerr, int32_t 
     int rode = 0;
     if (ride) {
         if ((e = wait_ar(ride, ss)) || (e = mark(ride_marks, ARCTOPK_MARK_PACKED_AR, ss))) return e;
-        e = arctopk::select_ride(p, p->b_sketch, ws, p->b_rowlist, p->b_slotmap, next, next_seed,
-                                 next ? next->b_V : nullptr, ride, ride->x_ws, ride->x_ef, ride->x_gerr,
-                                 ride->x_bucket, &rode, ss, keyed);
+        if (ride->x_w16)  // a bf16-wire ride is not handed to the select launch: its own, after it
+            e = arctopk::select_draw_keyed(p, p->b_sketch, ws, p->b_rowlist, p->b_slotmap, next, next_seed,
+                                           next ? next->b_V : nullptr, keyed, ss);
+        else
+            e = arctopk::select_ride(p, p->b_sketch, ws, p->b_rowlist, p->b_slotmap, next, next_seed,
+                                     next ? next->b_V : nullptr, ride, ride->x_ws, ride->x_ef, ride->x_gerr,
+                                     ride->x_bucket, &rode, ss, keyed);
         if (!e && rode) {
-            ride->x_deferred = ride->x_fin = 0;
-            ride->x_stream = nullptr;
+            x_clear(ride);
             e = mark(ride_marks, ARCTOPK_MARK_DECODE, ss);
         }
         if (!e && !rode) {  // a separate decode launch after the select
-            e = arctopk::decode_signal(ride, ride->b_packed, ride->b_slotmap, ride->x_ws, ride->x_ef, ride->x_gerr,
-                                       ride->x_bucket, ss, nullptr);
-            if (!e) {
-                ride->x_deferred = ride->x_fin = 0;
-                ride->x_stream = nullptr;
-            }
+            e = decode_step(ride, ride->x_w16 != 0, ride->x_ws, ride->x_ef, ride->x_gerr, ride->x_bucket, ss, nullptr);
+            if (!e) x_clear(ride);
             if (!e) e = mark(ride_marks, ARCTOPK_MARK_DECODE, ss);
         }
     } else {
@@ -854,6 +886,7 @@ int exchange_step(arctopk_plan* p, void* bucket, void* err, void* gerr, int32_t 
         carry->x_gerr = carry->x_t_gerr;
         carry->x_ef = carry->x_t_ef;
         carry->x_ws = 1;
+        carry->x_w16 = 0;
         carry->x_stream = side ? (void*)ss : nullptr;
     }
     if (!e) e = mark(marks, ARCTOPK_MARK_SELECT, st);
@@ -871,8 +904,11 @@ int exchange_step(arctopk_plan* p, void* bucket, void* err, void* gerr, int32_t 
         if ((e = ensure_event(&p->x_ev_packed, 0)) ||
             (e = ensure_event(&p->x_ev_ar, hipEventDisableTiming | hipEventReleaseToDevice)))
             return e;
-        e = arctopk::pack_signal(p, bucket, err, ef, p->b_rowlist, p->b_slotmap, p->b_packed, ss,
-                                 p->x_ev_packed);
+        // (the bf16 wire: k_w16_pack completes the event the same way; an empty table records it)
+        e = w16 ? arctopk::pack_wire16_signal(p, bucket, err, ef, err_in, p->b_rowlist, p->b_slotmap, p->b_packed16,
+                                              ss, p->x_ev_packed)
+                : arctopk::pack_signal(p, bucket, err, ef, p->b_rowlist, p->b_slotmap, p->b_packed, ss,
+                                       p->x_ev_packed);
         if (!e) Watchdog::get().watch(sketch_comm, p->x_ev_packed);
         // The backward's last step: its decode comes after its own packed all-reduce, the end of
         // the wire's work.  EF14 / noef: the bucket is dead once packed (EF14 packs the residual,
@@ -887,6 +923,10 @@ int exchange_step(arctopk_plan* p, void* bucket, void* err, void* gerr, int32_t 
             if (he != hipSuccess) return (int)he;
             p->x_fin = 3;
         }
+    } else if (w16) {
+        // the bf16 wire at world size 1: no fused finalize and no riding pack -- it packs to bf16 and
+        // decodes from it, so that one GPU produces what a rank of N would
+        e = arctopk_pack_wire16(p, bucket, err, ef, err_in, p->b_rowlist, p->b_slotmap, p->b_packed16, ss);
     } else if (!marks && ef != ARCTOPK_EF21) {
         // world size 1 (EF14 / noef): the all-reduce is the identity, so no packed buffer is
         // needed -- the decode (riding in a later select launch, or inline below) takes the
@@ -908,7 +948,9 @@ int exchange_step(arctopk_plan* p, void* bucket, void* err, void* gerr, int32_t 
     if (async_ar) {  // the index-free all-reduce of the packed values (:280) on its own stream
         hipError_t he = hipStreamWaitEvent(as, (hipEvent_t)p->x_ev_packed, 0);
         if (he != hipSuccess) return (int)he;
-        if ((e = arctopk_comm_allreduce(packed_comm, p->b_packed, p->info.packed_len, p->dtype, as))) return e;
+        if ((e = arctopk_comm_allreduce(packed_comm, w16 ? p->b_packed16 : p->b_packed, p->info.packed_len,
+                                        w16 ? ARCTOPK_BF16 : p->dtype, as)))
+            return e;
         he = hipEventRecord((hipEvent_t)p->x_ev_ar, as);
         if (he != hipSuccess) return (int)he;
         Watchdog::get().watch(packed_comm, p->x_ev_ar);
@@ -917,9 +959,10 @@ int exchange_step(arctopk_plan* p, void* bucket, void* err, void* gerr, int32_t 
     // the backward's last step (no deferral): the last deferred decode it finishes shares one
     // launch with its own decode, after its own packed all-reduce (unless markers were asked for)
     arctopk_plan* pair = nullptr;
-    if (!defer && !async_ar && nfinish > 0 && finish[nfinish - 1] && finish[nfinish - 1] != p &&
-        finish[nfinish - 1]->x_deferred && !(finish_marks && finish_marks[nfinish - 1]) && !marks &&
-        x_stream_of(finish[nfinish - 1], st) == ss)
+    // (a bf16-wire decode shares no launch: the pair is decoded one by one)
+    if (!w16 && !defer && !async_ar && nfinish > 0 && finish[nfinish - 1] && finish[nfinish - 1] != p &&
+        finish[nfinish - 1]->x_deferred && !finish[nfinish - 1]->x_w16 &&
+        !(finish_marks && finish_marks[nfinish - 1]) && !marks && x_stream_of(finish[nfinish - 1], st) == ss)
         pair = finish[nfinish - 1];
     // earlier buckets' deferred decodes the caller wants done now (in its order)
     for (int32_t i = 0; i < nfinish && !e; ++i)
@@ -933,13 +976,15 @@ int exchange_step(arctopk_plan* p, void* bucket, void* err, void* gerr, int32_t 
         p->x_gerr = gerr;
         p->x_ef = ef;
         p->x_ws = ws;
+        p->x_w16 = w16;
         p->x_stream = side ? (void*)ss : nullptr;
         return 0;
     }
     if (async_ar) {  // this step's own packed all-reduce, on the all-reduce stream
         if ((e = (int)hipStreamWaitEvent(ss, (hipEvent_t)p->x_ev_ar, 0))) return e;
     } else if (packed_comm) {
-        e = arctopk_comm_allreduce(packed_comm, p->b_packed, p->info.packed_len, p->dtype, ss);
+        e = arctopk_comm_allreduce(packed_comm, w16 ? p->b_packed16 : p->b_packed, p->info.packed_len,
+                                   w16 ? ARCTOPK_BF16 : p->dtype, ss);
     }
     if (!e) e = mark(marks, ARCTOPK_MARK_PACKED_AR, st);
     if (e) return e;
@@ -963,11 +1008,11 @@ int exchange_step(arctopk_plan* p, void* bucket, void* err, void* gerr, int32_t 
     }
     if (packed_comm) {  // the decode kernel completes x_ev_dec: the inline all-reduce is watched too
         if ((e = ensure_event(&p->x_ev_dec, hipEventDisableTiming | hipEventReleaseToDevice))) return e;
-        e = arctopk::decode_signal(p, p->b_packed, p->b_slotmap, ws, ef, gerr, bucket, ss, p->x_ev_dec);
+        e = decode_step(p, w16, ws, ef, gerr, bucket, ss, p->x_ev_dec);
         if (!e) Watchdog::get().watch(packed_comm, p->x_ev_dec);
         p->x_fin = 0;
     } else {
-        e = arctopk::decode_signal(p, p->b_packed, p->b_slotmap, ws, ef, gerr, bucket, ss, nullptr);
+        e = decode_step(p, w16, ws, ef, gerr, bucket, ss, nullptr);
         p->x_fin = 0;
     }
     if (!e) e = mark(marks, ARCTOPK_MARK_DECODE, st);

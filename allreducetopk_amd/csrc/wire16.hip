@@ -35,6 +35,12 @@
 //     (m % 4 != 0, an odd offset): the tile's contiguous element range in 16-B units across rows;
 //     rows of fewer than four columns and RAW tensors: a thread per row; DENSE segments: element
 //     tiles.
+//   scatter (the zero-ahead drain: out is already zero, NONE / EF14): the pack's chunks again, the
+//     other way round -- a thread reads 16 B of packed values (8 B at either end of a chunk whose
+//     packed values start 8 B off the 16-B grid) and stores their two 16-B units of out; element by
+//     element where the segment's `vec` does not hold.  2 B read and 4 B written per selected
+//     element, nothing else touched; no LDS.
+#include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -399,6 +405,96 @@ __global__ void __launch_bounds__(kW16Block) k_w16_decode(const SegDev* __restri
     else w16_dec_rows<EF, false>(s, t, packed, slotmap, sc, gerr, out);
 }
 
+// ---- zero-ahead scatter --------------------------------------------------------------------
+// out = mean on the selected elements only, into a bucket a memset zeroed while the packed values
+// were on the wire (exchange.cpp, x_fin 3): the pack's chunk table, read the other way round.
+__device__ __forceinline__ void w16_sc_elem(const bf16_t* __restrict__ p, const W16Scale sc, float* __restrict__ out,
+                                            int64_t el) {
+    const uint16_t w = __builtin_nontemporal_load(&p->u);
+    __builtin_nontemporal_store(sc(bf_bits_f(w)), out + el);
+}
+
+// The nu units of a chunk whose packed values are contiguous from p (8-B aligned): unit u's 4
+// elements go to bucket element dst(u), or dst(u) < 0: the unit is skipped.  A thread takes a pair of
+// units whose packed 16 B are aligned (one 16-B load), a lone unit at either end of the chunk (one
+// 8-B load); the step's loads are issued before its two 16-B stores.
+template <class Dst>
+__device__ __forceinline__ void w16_sc_pairs(const bf16_t* __restrict__ p, int nu, const W16Scale sc,
+                                             float* __restrict__ out, Dst dst) {
+    const int head = ((uintptr_t)p & 15) ? 1 : 0;
+    const int nitems = (nu + head + 1) / 2;
+    for (int it = threadIdx.x; it < nitems; it += kW16Block) {
+        const int ua = 2 * it - head, ub = ua + 1;
+        const int64_t ea = ua >= 0 ? dst(ua) : -1, eb = ub < nu ? dst(ub) : -1;
+        u2_t wa = u2_t{0u, 0u}, wb = u2_t{0u, 0u};
+        if (ea >= 0 && eb >= 0) {
+            const u4_t w = __builtin_nontemporal_load(reinterpret_cast<const u4_t*>(p + 4 * (int64_t)ua));
+            wa = u2_t{w.x, w.y};
+            wb = u2_t{w.z, w.w};
+        } else if (ea >= 0) {
+            wa = __builtin_nontemporal_load(reinterpret_cast<const u2_t*>(p + 4 * (int64_t)ua));
+        } else if (eb >= 0) {
+            wb = __builtin_nontemporal_load(reinterpret_cast<const u2_t*>(p + 4 * (int64_t)ub));
+        }
+        if (ea >= 0) st_f4_nt(out + ea, w16_mean4(wa, sc));
+        if (eb >= 0) st_f4_nt(out + eb, w16_mean4(wb, sc));
+    }
+}
+
+__global__ void __launch_bounds__(kW16Block) k_w16_scatter(const SegDev* __restrict__ segs,
+                                                          const W16Chunk* __restrict__ chunks,
+                                                          const bf16_t* __restrict__ packed,
+                                                          const int32_t* __restrict__ rowlist, const W16Scale sc,
+                                                          float* __restrict__ out) {
+    const W16Chunk ch = chunks[blockIdx.x];
+    const SegDev& s = segs[ch.seg];
+    const int m = (int)s.m;
+    if (ch.mode == W16P_DENSE) {  // every element is selected
+        const int64_t e0 = s.offset + ch.j0;
+        const bf16_t* p = packed + s.packed_off + ch.j0;
+        int done = 0;
+        if (s.offset % 4 == 0 && s.packed_off % 4 == 0) {  // (chunks start at multiples of 8 elements)
+            const int nu = ch.nj / 4;
+            w16_sc_pairs(p, nu, sc, out, [&](int u) { return e0 + 4 * (int64_t)u; });
+            done = nu * 4;
+        }
+        for (int i = done + (int)threadIdx.x; i < ch.nj; i += kW16Block) w16_sc_elem(p + i, sc, out, e0 + i);
+        return;
+    }
+    const int32_t* rl = rowlist + s.sel_off + ch.j0;
+    const bf16_t* p = packed + s.packed_off + ch.j0 * (int64_t)m;
+    if (ch.mode == W16P_ROWS_VEC) {
+        if (m % 8 == 0 && ((uintptr_t)p & 15) == 0) {  // 8 elements of one row per thread: one 16-B packed load
+            const int U8 = m / 8, n8 = ch.nj * U8;
+            for (int u = threadIdx.x; u < n8; u += kW16Block) {
+                const int jj = u / U8, c8 = u - jj * U8;
+                const int64_t row = rl[jj];
+                if ((uint64_t)row >= (uint64_t)s.n) continue;  // (never, for a select's row list)
+                const int64_t el = s.offset + row * (int64_t)m + 8 * c8;
+                const u4_t w = __builtin_nontemporal_load(reinterpret_cast<const u4_t*>(p + 8 * (int64_t)u));
+                st_f4_nt(out + el, w16_mean4(u2_t{w.x, w.y}, sc));
+                st_f4_nt(out + el + 4, w16_mean4(u2_t{w.z, w.w}, sc));
+            }
+            return;
+        }
+        const int U = m / 4;
+        w16_sc_pairs(p, ch.nj * U, sc, out, [&](int u) -> int64_t {
+            const int jj = u / U, c4 = u - jj * U;
+            const int64_t row = rl[jj];
+            if ((uint64_t)row >= (uint64_t)s.n) return -1;  // (never, for a select's row list)
+            return s.offset + row * (int64_t)m + 4 * c4;
+        });
+        return;
+    }
+    const int ne = ch.nj * m;
+    for (int i = threadIdx.x; i < ne; i += kW16Block) {
+        const int jj = i / m, c = i - jj * m;
+        const int64_t row = rl[jj];
+        if ((uint64_t)row >= (uint64_t)s.n) continue;
+        w16_sc_elem(p + i, sc, out, s.offset + row * (int64_t)m + c);
+    }
+}
+
 // ---- the plan's tables ---------------------------------------------------------------------
 void w16_free(W16Tab* t) {
     if (t->d_chunks) (void)hipFree(t->d_chunks);
@@ -449,12 +545,29 @@ int w16_table(const arctopk_plan* p, W16Tab** out) {
     return 0;
 }
 
+// a launch that completes `done` itself when given one (hipExtLaunchKernelGGL's stop event: no
+// marker packet on the stream)
+template <typename... KArgs, typename... Args>
+void w16_launch(void (*k)(KArgs...), int n, void* stream, void* done, Args... args) {
+    if (done)
+        hipExtLaunchKernelGGL(k, dim3((unsigned)n), dim3(kW16Block), 0, (hipStream_t)stream, nullptr,
+                              (hipEvent_t)done, 0, args...);
+    else
+        hipLaunchKernelGGL(k, dim3((unsigned)n), dim3(kW16Block), 0, (hipStream_t)stream, args...);
+}
+
 template <int EF>
 void launch_pack(const arctopk_plan* p, const W16Tab* t, const void* grad, void* err, int32_t err_in,
-                 const int32_t* rowlist, void* packed, void* stream) {
-    hipLaunchKernelGGL((k_w16_pack<EF>), dim3((unsigned)t->n_chunks), dim3(kW16Block), 0, (hipStream_t)stream,
-                       p->d_segs, t->d_chunks, static_cast<const float*>(grad), static_cast<float*>(err), (int)err_in,
-                       rowlist, static_cast<bf16_t*>(packed));
+                 const int32_t* rowlist, void* packed, void* stream, void* done) {
+    w16_launch(&k_w16_pack<EF>, t->n_chunks, stream, done, (const SegDev*)p->d_segs, (const W16Chunk*)t->d_chunks,
+               static_cast<const float*>(grad), static_cast<float*>(err), (int)err_in, rowlist,
+               static_cast<bf16_t*>(packed));
+}
+
+// what an empty work table leaves to do: `done` recorded, if given
+int w16_nothing(int st, void* stream, void* done) {
+    if (st != 0 || !done) return st;
+    return (int)hipEventRecord((hipEvent_t)done, (hipStream_t)stream);
 }
 
 }  // namespace
@@ -467,8 +580,9 @@ void wire16_forget(arctopk_plan* p) {
 }
 }  // namespace arctopk
 
-extern "C" int arctopk_pack_wire16(const arctopk_plan* p, const void* grad, void* err, int32_t ef, int32_t err_in,
-                                   const int32_t* rowlist, const int32_t* slotmap, void* packed, void* stream) {
+namespace arctopk {
+int pack_wire16_signal(const arctopk_plan* p, const void* grad, void* err, int32_t ef, int32_t err_in,
+                       const int32_t* rowlist, const int32_t* slotmap, void* packed, void* stream, void* done) {
     if (!p || p->dtype != ARCTOPK_F32 || !ef_known(ef) || (err_in != 0 && err_in != 1)) return ARCTOPK_EINVAL;
     if (!rowlist || !slotmap || !packed) return ARCTOPK_EINVAL;
     if (ef != ARCTOPK_EF_NONE && !err) return ARCTOPK_EINVAL;
@@ -477,29 +591,64 @@ extern "C" int arctopk_pack_wire16(const arctopk_plan* p, const void* grad, void
     if (low_bits(grad, 15) | low_bits(err, 15) | low_bits(packed, 7)) return ARCTOPK_EINVAL;
     W16Tab* t = nullptr;
     const int st = w16_table(p, &t);
-    if (st != 0 || t->n_chunks == 0) return st;
-    if (ef == ARCTOPK_EF14) launch_pack<W16_EF14>(p, t, grad, err, err_in, rowlist, packed, stream);
-    else if (ef == ARCTOPK_EF21) launch_pack<W16_EF21>(p, t, grad, err, err_in, rowlist, packed, stream);
-    else launch_pack<W16_NONE>(p, t, grad, err, err_in, rowlist, packed, stream);
+    if (st != 0 || t->n_chunks == 0) return w16_nothing(st, stream, done);
+    if (ef == ARCTOPK_EF14) launch_pack<W16_EF14>(p, t, grad, err, err_in, rowlist, packed, stream, done);
+    else if (ef == ARCTOPK_EF21) launch_pack<W16_EF21>(p, t, grad, err, err_in, rowlist, packed, stream, done);
+    else launch_pack<W16_NONE>(p, t, grad, err, err_in, rowlist, packed, stream, done);
     return (int)hipGetLastError();
+}
+
+int decode_wire16_signal(const arctopk_plan* p, const void* packed, const int32_t* rowlist, const int32_t* slotmap,
+                         int32_t world_size, int32_t ef, void* gerr, void* out, bool scatter, void* stream,
+                         void* done) {
+    if (!p || p->dtype != ARCTOPK_F32 || !ef_known(ef) || world_size < 1) return ARCTOPK_EINVAL;
+    if (!packed || !slotmap || !out || (ef == ARCTOPK_EF21 && !gerr)) return ARCTOPK_EINVAL;
+    if (scatter && (!rowlist || ef == ARCTOPK_EF21)) return ARCTOPK_EINVAL;  // (EF21 writes gE everywhere)
+    if (low_bits(gerr, 15) | low_bits(out, 15) | low_bits(packed, 7)) return ARCTOPK_EINVAL;
+    W16Tab* t = nullptr;
+    const int st = w16_table(p, &t);
+    if (st != 0 || (scatter ? t->n_chunks : t->n_tiles) == 0) return w16_nothing(st, stream, done);
+    const W16Scale sc = make_mean_scale(world_size);
+    const SegDev* segs = p->d_segs;
+    const W16Tile* tiles = t->d_tiles;
+    const bf16_t* pk = static_cast<const bf16_t*>(packed);
+    float *ge = static_cast<float*>(gerr), *o = static_cast<float*>(out);
+    if (scatter)
+        w16_launch(&k_w16_scatter, t->n_chunks, stream, done, segs, (const W16Chunk*)t->d_chunks, pk, rowlist, sc, o);
+    else if (ef == ARCTOPK_EF21)
+        w16_launch(&k_w16_decode<W16_EF21>, t->n_tiles, stream, done, segs, tiles, pk, slotmap, sc, ge, o);
+    else
+        w16_launch(&k_w16_decode<W16_NONE>, t->n_tiles, stream, done, segs, tiles, pk, slotmap, sc, ge, o);
+    return (int)hipGetLastError();
+}
+}  // namespace arctopk
+
+extern "C" int arctopk_pack_wire16(const arctopk_plan* p, const void* grad, void* err, int32_t ef, int32_t err_in,
+                                   const int32_t* rowlist, const int32_t* slotmap, void* packed, void* stream) {
+    return pack_wire16_signal(p, grad, err, ef, err_in, rowlist, slotmap, packed, stream, nullptr);
 }
 
 extern "C" int arctopk_decode_wire16(const arctopk_plan* p, const void* packed, const int32_t* slotmap,
                                      int32_t world_size, int32_t ef, void* gerr, void* out, void* stream) {
-    if (!p || p->dtype != ARCTOPK_F32 || !ef_known(ef) || world_size < 1) return ARCTOPK_EINVAL;
-    if (!packed || !slotmap || !out || (ef == ARCTOPK_EF21 && !gerr)) return ARCTOPK_EINVAL;
-    if (low_bits(gerr, 15) | low_bits(out, 15) | low_bits(packed, 7)) return ARCTOPK_EINVAL;
-    W16Tab* t = nullptr;
-    const int st = w16_table(p, &t);
-    if (st != 0 || t->n_tiles == 0) return st;
-    const W16Scale sc = make_mean_scale(world_size);
-    const dim3 grid((unsigned)t->n_tiles), block(kW16Block);
-    const bf16_t* pk = static_cast<const bf16_t*>(packed);
-    if (ef == ARCTOPK_EF21)
-        hipLaunchKernelGGL((k_w16_decode<W16_EF21>), grid, block, 0, (hipStream_t)stream, p->d_segs, t->d_tiles, pk,
-                           slotmap, sc, static_cast<float*>(gerr), static_cast<float*>(out));
-    else
-        hipLaunchKernelGGL((k_w16_decode<W16_NONE>), grid, block, 0, (hipStream_t)stream, p->d_segs, t->d_tiles, pk,
-                           slotmap, sc, static_cast<float*>(gerr), static_cast<float*>(out));
-    return (int)hipGetLastError();
+    return decode_wire16_signal(p, packed, nullptr, slotmap, world_size, ef, gerr, out, false, stream, nullptr);
+}
+
+extern "C" int arctopk_decode_wire16_scatter(const arctopk_plan* p, const void* packed, const int32_t* rowlist,
+                                             const int32_t* slotmap, int32_t world_size, void* out, void* stream) {
+    return decode_wire16_signal(p, packed, rowlist, slotmap, world_size, ARCTOPK_EF_NONE, nullptr, out, true, stream,
+                                nullptr);
+}
+
+extern "C" int arctopk_plan_bind_wire16(arctopk_plan* p, void* packed) {
+    if (!p || p->dtype != ARCTOPK_F32 || low_bits(packed, 7)) return ARCTOPK_EINVAL;
+    if (p->x_deferred || p->x_trail) return ARCTOPK_EINVAL;  // the caller finishes the plan's step first
+    p->b_packed16 = packed;
+    return 0;
+}
+
+// Diagnostics: exchange steps of `p` whose decode was the zero-ahead scatter so far
+extern "C" int arctopk_diag_wire16_scatters(const arctopk_plan* p, int64_t* count) {
+    if (!p || !count) return ARCTOPK_EINVAL;
+    *count = p->w16_scatters;
+    return 0;
 }

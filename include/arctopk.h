@@ -357,6 +357,15 @@ int arctopk_comm_allreduce(arctopk_comm* comm, void* buf, int64_t count, int32_t
  *   or fused finalize (world size 1), on the stream it is enqueued on; a finalize that rides in a
  *   later step's select on a select stream, a carried trailing step and the groups of a bucket
  *   leave the next encode on the caller's stream to run as 1.
+ * A plan bound with arctopk_plan_bind_wire16 runs the step on the bf16 wire: the pack is
+ *   arctopk_pack_wire16's (completing the same event), the packed all-reduce moves the bound bf16
+ *   buffer as ARCTOPK_BF16 under the same rules, and the decode is arctopk_decode_wire16's -- by
+ *   arctopk_exchange_finish when deferred, a separate launch after the select when the plan is a
+ *   later step's `ride` (whatever that step's plan), never paired -- or, for the backward's last
+ *   step under the zero-ahead conditions, arctopk_decode_wire16_scatter.  World size 1 without
+ *   communicators packs to bf16 and decodes from it.  ARCTOPK_EINVAL, before anything is enqueued,
+ *   for err_in other than 0 / 1, a `sel_stream` other than `stream`, a bound plan as `trail`, and
+ *   bucket / err / gerr not 16-B aligned; a `trail` is enqueued on its own, never carried.
  * Replaces: the whole of group_topk_hook's compressed path (:254-290) given the seed.
  */
 int arctopk_exchange_step(arctopk_plan* plan, void* bucket, void* err, void* gerr, int32_t ef,
@@ -782,6 +791,30 @@ int arctopk_pack_wire16(const arctopk_plan* plan, const void* grad, void* err, i
                         const int32_t* rowlist, const int32_t* slotmap, void* packed_bf16, void* stream);
 int arctopk_decode_wire16(const arctopk_plan* plan, const void* packed_bf16, const int32_t* slotmap,
                           int32_t world_size, int32_t ef, void* gerr, void* out, void* stream);
+/*
+ * The bf16-wire decode of NONE / EF14 into an `out` that is already zero (the zero-ahead drain of
+ * the exchange step's last bucket): for every selected row (rowlist: arctopk_select's; every entry is
+ * checked against the segment's rows), every selected element of a RAW segment and every element of
+ * a DENSE segment, out = f(P) / world_size, the mean arctopk_decode_wire16 forms; nothing else is
+ * read or written (2 B read and 4 B written per selected element, against 4 B per bucket element
+ * plus 2 B per selected one for the whole decode).  The result equals arctopk_decode_wire16's with
+ * ef NONE or EF14 when `out` was zero.  ARCTOPK_EINVAL for a null plan or one that is not
+ * ARCTOPK_F32, a null packed_bf16 / rowlist / slotmap / out, world_size < 1, `out` not 16-B aligned
+ * or packed_bf16 not 8-B aligned; nothing is enqueued then.  `slotmap` is not read.
+ */
+int arctopk_decode_wire16_scatter(const arctopk_plan* plan, const void* packed_bf16, const int32_t* rowlist,
+                                  const int32_t* slotmap, int32_t world_size, void* out, void* stream);
+/*
+ * Binds `packed_bf16` (8-B aligned, packed_len bf16 elements, the plan's packed layout; NULL
+ * unbinds) to an ARCTOPK_F32 plan: its exchange steps (arctopk_exchange_step) then run on the bf16
+ * wire -- the pack is arctopk_pack_wire16's, the packed all-reduce moves `packed_bf16` as
+ * ARCTOPK_BF16 and the decode is arctopk_decode_wire16's (arctopk_decode_wire16_scatter for the
+ * zero-ahead drain) -- with the deferral, all-reduce stream and watchdog of any other step.  Such a
+ * step takes no select stream, no trailing step's launches, no err_in = 2, and its decode rides in
+ * no other launch.  ARCTOPK_EINVAL for a plan that is not ARCTOPK_F32, a misaligned buffer, or a
+ * plan with a step deferred or trailing.  A plan without the binding runs the default step.
+ */
+int arctopk_plan_bind_wire16(arctopk_plan* plan, void* packed_bf16);
 
 /*
  * Device projections of one bucket call: for every SKETCH segment in bucket order,
@@ -868,6 +901,9 @@ int arctopk_diag_host_times(int64_t* ns, int32_t n, int64_t* calls);
 /* Encode launches of `plan` so far that ran the zero-rows kernel (err_in = 2 accepted; see
  * arctopk_encode).  Tests use it to show the path was taken or refused. */
 int arctopk_diag_zero_row_encodes(const arctopk_plan* plan, int64_t* count);
+/* Exchange steps of `plan` so far whose decode was the bf16-wire zero-ahead scatter
+ * (arctopk_plan_bind_wire16, arctopk_decode_wire16_scatter). */
+int arctopk_diag_wire16_scatters(const arctopk_plan* plan, int64_t* count);
 /* Which encode paths `plan` holds, from its host-side bookkeeping (nothing is launched):
  * out[0 .. min(n, ARCTOPK_DIAG_ENCODE_TILES)) =
  *   [0] .. [3]  encode tiles of the plan's default table per mode: 1-D pass-through (RAW),

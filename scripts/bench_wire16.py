@@ -16,7 +16,12 @@ pattern in that file.
 
 Whole call: one backward of four headline buckets through group_topk_hook (EF14, r 4) beside the
 emulated 8-rank wire (emulate_wire = dict(ranks=8, busbw_gbs=350)): the default pipelined path, the
-default path with async_exchange = False (inline, like for like) and wire_dtype = bf16 (inline).
+default path with async_exchange = False (inline, like for like), wire_dtype = bf16 (inline) and
+wire_dtype = bf16 with wire_exchange = "step" (the bf16 wire through the exchange step: pipelined).
+
+Scatter: arctopk_decode_wire16 (noef / EF14, the whole decode: 4 N + 2 K bytes) against
+arctopk_decode_wire16_scatter (the zero-ahead drain's decode into a zeroed bucket: 6 K bytes), the
+same way as the other kernel rows.
 
     python scripts/bench_wire16.py --stream profiles/wire16/stream_wire16.txt --out profiles/wire16/table.txt
 """
@@ -134,10 +139,16 @@ def main():
                                                              Es[i % SETS].data_ptr() if ef == N.EF21 else None,
                                                              Os[i % SETS].data_ptr(), sid), "arctopk_decode_wire16")
 
+        def scat16(i):
+            N.check(L.arctopk_decode_wire16_scatter(plan.handle, P16[i % SETS].data_ptr(), rl, sm, 1,
+                                                    Os[i % SETS].data_ptr(), sid), "arctopk_decode_wire16_scatter")
+
         rows = [("pack ef14", pack32(N.EF14), pack16(N.EF14), 12 * k, 10 * k, "rw8w2"),
                 ("pack ef21", pack32(N.EF21), pack16(N.EF21), 16 * k, 14 * k, "r4rw8w2"),
                 ("decode ef14", dec32(N.EF14), dec16(N.EF14), 4 * n + 4 * k, 4 * n + 2 * k, "w4r2"),
-                ("decode ef21", dec32(N.EF21), dec16(N.EF21), 8 * n + 8 * k, 8 * n + 6 * k, None)]
+                ("decode ef21", dec32(N.EF21), dec16(N.EF21), 8 * n + 8 * k, 8 * n + 6 * k, None),
+                # (left: the whole bf16-wire decode; right: the scatter of the same packed values)
+                ("w16 scatter", dec16(N.EF14), scat16, 4 * n + 2 * k, 6 * k, "r2w4")]
         for what, fa, fb, ba, bb, pat in rows:
             t = ab({"a": fa, "b": fb}, args)
             ma, mb = statistics.median(t["a"]), statistics.median(t["b"])
@@ -150,7 +161,8 @@ def main():
     if not args.no_hook:
         shapes, ratio = LOADS["headline"]
         n = bucket_numel(shapes)
-        configs = {"pipelined": dict(), "inline": dict(async_exchange=False), "wire16": dict(wire_dtype=BF16)}
+        configs = {"pipelined": dict(), "inline": dict(async_exchange=False), "wire16": dict(wire_dtype=BF16),
+                   "wire16_step": dict(wire_dtype=BF16, wire_exchange="step")}
         states, buckets = {}, {}
         for kname, kw in configs.items():
             st = G.GroupTopKState(None, r=4, compress_ratio=ratio, start_compress_iter=0, use_error_feedback="ef14",
@@ -170,6 +182,8 @@ def main():
             return fn
         t = ab({kname: step(kname) for kname in configs}, args)
         assert states["wire16"].wire16_calls > 0 and states["pipelined"].wire16_calls == 0
+        assert states["wire16_step"].wire16_step_calls == states["wire16_step"].wire16_calls > 0
+        assert states["wire16"].wire16_step_calls == 0
         base = statistics.median(t["pipelined"])
         lines.append("# one backward of four headline fp32 buckets (EF14) beside the emulated wire (8 ranks, 350 GB/s "
                      "busBW); GB/s = bucket bytes / median (bench.py's figure of merit); x: time against the pipelined default")
@@ -182,6 +196,12 @@ def main():
         lines.append("# the inline bf16-wire branch %s the pipelined default beside the wire (%.0f us against %.0f us); "
                      "against the inline default it takes %.2f of the time"
                      % ("beats" if mw < base else "does not beat", mw, base, mw / mi))
+        ts = t["wire16_step"]
+        ms = statistics.median(ts)
+        spread = max(max(ts) - min(ts), max(t["wire16"]) - min(t["wire16"]))
+        lines.append("# the bf16 wire through the exchange step: %.1f us against the inline bf16-wire branch's %.1f us "
+                     "(margin %.1f us, the larger of the two lines' max - min %.1f us); against the pipelined default "
+                     "x %.2f (its minimum %.1f us)" % (ms, mw, mw - ms, spread, ms / base, min(t["pipelined"])))
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as fh:
         fh.write("\n".join(lines) + "\n")

@@ -7,6 +7,8 @@
 //   r4rw8w2: 16 B of a second fp32 array read as well (the EF21 pack: 14 B per element)
 //   w4r2   : 16 B of fp32 written for every unit, 8 B of bf16 read for one unit in five (the noef /
 //            EF14 decode at ratio 0.2: 4 N + 2 K bytes)
+//   r2w4   : 8 B of bf16 read and 16 B of fp32 written for the first fifth of the units, contiguous
+//            (the zero-ahead scatter at ratio 0.2, arctopk_decode_wire16_scatter: 6 K bytes)
 //   hipcc --offload-arch=gfx950 -O3 scripts/stream_wire16.hip -o scripts/stream_wire16
 //   ./scripts/stream_wire16 [Mi elements per array] [sets]
 #include <hip/hip_runtime.h>
@@ -62,6 +64,15 @@ __global__ void __launch_bounds__(256) k_decode(const v2u* __restrict__ p, v4f* 
     }
 }
 
+__global__ void __launch_bounds__(256) k_scatter(const v2u* __restrict__ p, v4f* __restrict__ out, size_t k4) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < k4; i += (size_t)gridDim.x * 256) {
+        const v2u w = __builtin_nontemporal_load(p + i);
+        __builtin_nontemporal_store(v4f{__uint_as_float(w.x << 16), __uint_as_float(w.x & 0xFFFF0000u),
+                                        __uint_as_float(w.y << 16), __uint_as_float(w.y & 0xFFFF0000u)},
+                                    out + i);
+    }
+}
+
 int main(int argc, char** argv) {
     const size_t mi = argc > 1 ? (size_t)std::atoll(argv[1]) : 64;
     const int sets = argc > 2 ? std::atoi(argv[2]) : 4;
@@ -79,9 +90,9 @@ int main(int argc, char** argv) {
     CK(hipEventCreate(&e0));
     CK(hipEventCreate(&e1));
     std::printf("%zu Mi elements per array, %d sets, cold\n", mi, sets);
-    const char* names[3] = {"rw8w2", "r4rw8w2", "w4r2"};
-    const double bytes[3] = {n * 10.0, n * 14.0, n * 4.0 + (n / 5) * 2.0};
-    for (int pat = 0; pat < 3; ++pat) {
+    const char* names[4] = {"rw8w2", "r4rw8w2", "w4r2", "r2w4"};
+    const double bytes[4] = {n * 10.0, n * 14.0, n * 4.0 + (n / 5) * 2.0, (n / 5) * 6.0};
+    for (int pat = 0; pat < 4; ++pat) {
         for (unsigned grid : {2048u, 4096u, 8192u, 16384u}) {
             std::vector<float> us;
             for (int it = 0; it < 24; ++it) {
@@ -93,8 +104,11 @@ int main(int argc, char** argv) {
                 else if (pat == 1)
                     hipLaunchKernelGGL(k_pack<true>, dim3(grid), dim3(256), 0, nullptr, (const v4f*)G[s], (v4f*)E[s],
                                        (v2u*)P[s], n4);
-                else
+                else if (pat == 2)
                     hipLaunchKernelGGL(k_decode, dim3(grid), dim3(256), 0, nullptr, (const v2u*)P[s], (v4f*)E[s], n4);
+                else
+                    hipLaunchKernelGGL(k_scatter, dim3(grid), dim3(256), 0, nullptr, (const v2u*)P[s], (v4f*)E[s],
+                                       n4 / 5);
                 CK(hipEventRecord(e1, nullptr));
                 CK(hipEventSynchronize(e1));
                 float ms = 0;
