@@ -155,6 +155,12 @@ _SIGS = {
     "arctopk_sparse_decode_mixed21": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, POINTER(c_int64),
                                                 POINTER(c_int64), POINTER(c_int64), c_int64, c_void_p, c_void_p,
                                                 c_int32, c_int32, c_float, c_void_p]),
+    "arctopk_sparse_pack_wire16": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, POINTER(c_int64),
+                                             POINTER(c_int64), POINTER(c_int64), c_void_p, c_void_p, c_int32,
+                                             c_float, c_void_p]),
+    "arctopk_sparse_decode_wire16": (c_int32, [c_void_p, c_int64, c_int32, POINTER(c_int64), POINTER(c_int64),
+                                               POINTER(c_int64), c_int64, c_void_p, c_void_p, c_int32, c_int32,
+                                               c_int32, c_void_p, c_float, c_void_p]),
     "arctopk_ef_apply": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p]),
     "arctopk_draw_bf16_normal": (c_int32, [c_uint64, c_int64, c_void_p]),
     "arctopk_draw_normal": (c_int32, [c_uint64, c_int32, c_int32, POINTER(c_int64), c_void_p]),

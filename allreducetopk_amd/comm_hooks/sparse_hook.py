@@ -56,6 +56,24 @@ bucket's ``error_dict[b]`` -- and under EF21 ``global_error_dict[b]`` -- in fp32
 
 with the bf16 wire, the index exchange and the bit accounting of the default path.  The option is
 ignored for fp32 buckets and "noef", and refused with ``large_batch_init`` on a bf16 bucket.
+
+``SparseState.wire_dtype = torch.bfloat16`` (not in the reference; environment
+default ``ARCTOPK_SPARSE_WIRE_DTYPE=bf16``) sends an fp32 bucket's values as bf16, as
+``GroupTopKState.wire_dtype`` does for ARC-TopK: RandK's all-reduce carries half the bytes, TopK's
+all-gathers three quarters (the indices stay int32).  Fold and selection are the fp32 path's, bit
+for bit; behind them such a call runs
+
+    pack    arctopk_sparse_pack_wire16  vals16 = b(values); EF14: E[idx] := values - f(vals16), the
+            remainder of the rounding | EF21: E[idx] := fma(decay, f(vals16), E[idx])
+            (in place of arctopk_sparse_residual)
+    RandK : all_reduce(vals16) | TopK: all_gather(vals16), all_gather(indices)
+    decode  arctopk_sparse_decode_wire16  fp32 rank-ordered sums of f(vals16), / ws, EF21's gE; where
+            every tensor's indices ascend (TopK, RandK "hash"; not the column layout) one block
+            composes a whole chunk from all ranks in LDS and writes it once
+
+also at world size 1, so one GPU produces what a rank of N would.  Residuals stay plain fp32.  The
+option is ignored for bf16 buckets (their wire is bf16 already), in the dense warm-up calls and in
+EF21's dense first call of a bucket, and refused with ``large_batch_init`` on an fp32 bucket.
 """
 
 import logging
@@ -152,6 +170,14 @@ class SparseState(HookState):
         self.mixed_calls = 0  # compressed calls that ran with fp32 residuals under a bf16 bucket
         self._mixed_buckets = set()  # ... and the buckets whose residuals are such
         self._mixed_scratch = None  # EF21: D = f(G) - E, then the decode's fp32 sums (grown, never shrunk)
+        # Wire dtype (not in the reference): None sends an fp32 bucket's values
+        # as fp32; torch.bfloat16 sends them as bf16 and keeps the rounding remainder of what was sent
+        # in the residual.  Ignored for bf16 buckets.
+        env = os.environ.get("ARCTOPK_SPARSE_WIRE_DTYPE", "")
+        if env not in ("", "bf16"):
+            raise ValueError(f"ARCTOPK_SPARSE_WIRE_DTYPE must be 'bf16' (or unset), got {env!r}")
+        self.wire_dtype = torch.bfloat16 if env == "bf16" else None
+        self.wire16_calls = 0  # compressed calls that sent bf16 values of an fp32 bucket
 
     # ratio of this call; the c4 variant overrides (gradual compression)
     def _call_ratio(self) -> float:
@@ -169,8 +195,18 @@ class SparseState(HookState):
             raise ValueError(f"error_dtype must be None or torch.float32, got {ed!r}")
         return ed is not None and bucket_dtype == torch.bfloat16 and ef != N.EF_NONE
 
+    def _wire16(self, bucket_dtype) -> bool:
+        """Whether this call sends bf16 values of an fp32 bucket.  ValueError for a ``wire_dtype``
+        other than None / torch.bfloat16; ignored for bf16 buckets."""
+        wd = self.wire_dtype
+        if wd is not None and wd is not torch.bfloat16:
+            raise ValueError(f"wire_dtype must be None or torch.bfloat16, got {wd!r}")
+        return wd is not None and bucket_dtype == torch.float32
+
     def state_dict(self) -> dict:
         out = super().state_dict()
+        # for information: the residuals are plain fp32 either way, so loading needs no rule
+        out["wire_dtype"] = "bf16" if self.wire_dtype is torch.bfloat16 else None
         # the residual dtype option, and the buckets whose fp32 residuals belong to a bf16 bucket
         out["error_dtype"] = "fp32" if self.error_dtype is torch.float32 else None
         out["mixed_buckets"] = sorted(self._mixed_buckets)
@@ -280,6 +316,9 @@ def _sparse_hook_impl(state: SparseState, bucket, c4: bool = False) -> "torch.fu
         if state._mixed_residual(bucket.buffer().dtype, N.EF21):
             raise ValueError("error_dtype=torch.float32 does not run with large_batch_init: that hook "
                              "keeps a bfloat16 bucket's residuals in bfloat16")
+        if state._wire16(bucket.buffer().dtype):
+            raise ValueError("wire_dtype=torch.bfloat16 does not run with large_batch_init: that hook "
+                             "keeps a float32 bucket's float32 wire")
         return _large_batch_ef21(state, bucket, c4)
     state.maybe_accumulate_momentum_on_bucket(bucket)
     group = state.process_group if state.process_group is not None else dist.group.WORLD
@@ -302,6 +341,7 @@ def _sparse_hook_impl(state: SparseState, bucket, c4: bool = False) -> "torch.fu
     dt = N.DTYPE_CODE[dtype]
     # EF21 residual scaling: E += error_decay * C(D), gE += error_decay * out (:265, :296)
     decay = float(state.error_decay)
+    wire16 = state._wire16(dtype)  # bf16 values of this fp32 bucket on the wire (wire_dtype)
 
     if state._mixed_residual(dtype, ef):  # fp32 residuals under this bf16 bucket (error_dtype)
         return _mixed_call(state, bucket, group, world_size, ef, decay)
@@ -344,7 +384,8 @@ def _sparse_hook_impl(state: SparseState, bucket, c4: bool = False) -> "torch.fu
         seed = torch.randint(0, 1_000_000_000, (1,), generator=state.rng).item()
         torch.manual_seed(seed)
     _compress_exchange(state, bucket, group, world_size, ef, state._call_ratio(), seed,
-                       e_decay=decay, g_decay=decay, count_bits=True, ef14_folded=ef == N.EF14)
+                       e_decay=decay, g_decay=decay, count_bits=True, ef14_folded=ef == N.EF14, wire16=wire16)
+    state.wire16_calls += int(wire16)
     state.maybe_increase_iter(bucket)
     fut = torch.futures.Future()
     fut.set_result(input_tensor)
@@ -512,7 +553,7 @@ def _mixed_call(state: SparseState, bucket, group, world_size: int, ef: int,
 
 def _compress_exchange(state: SparseState, bucket, group, world_size: int, ef: int, ratio: float,
                        seed, e_decay: float, g_decay: float, count_bits: bool, on_values=None,
-                       ef14_folded: bool = False) -> None:
+                       ef14_folded: bool = False, wire16: bool = False) -> None:
     """The compressed call after the EF pre-apply, on the caller's stream: select (TopK) or draw
     (RandK) the indices, gather the values, persist the residual (EF14: E[idx] = 0; EF21:
     E[idx] += e_decay * values), exchange (RandK: all-reduce; TopK: all-gather of values and
@@ -520,6 +561,10 @@ def _compress_exchange(state: SparseState, bucket, group, world_size: int, ef: i
     ``sparse_type`` "row" / "column": the per-segment select (arctopk_seg_select) with the tensors'
     totals as ``ks``; under EF14 the caller has folded E := G + E already and says so with
     ``ef14_folded`` (the tensor path's fused folds go by ``state._fold_in`` as before).
+    ``wire16`` (an fp32 bucket under ``wire_dtype=torch.bfloat16``): after the unchanged select,
+    arctopk_sparse_pack_wire16 rounds the values to bf16 and writes the residual in place of
+    arctopk_sparse_residual; the values travel and count as 16 bits; arctopk_sparse_decode_wire16
+    decodes.
     Reference: sparse_hook.py:237-297 (and :363-410 for the large-batch hook)."""
     L = N.lib()
     input_tensor = bucket.buffer()
@@ -533,6 +578,7 @@ def _compress_exchange(state: SparseState, bucket, group, world_size: int, ef: i
     seg, numels, ks, offsets, k_off, sum_k = _bucket_layout(state, input_tensor, tensors, ratio)
     nt = len(tensors)
     fold14 = ef == N.EF14  # the pre-compression bucket lives in E (arctopk_ef14_fold)
+    value_bits = 16 if wire16 else dtype_bits(dtype)
     a_off, a_n, a_k, a_ko = (N.i64_array(offsets), N.i64_array(numels), N.i64_array(ks),
                              N.i64_array(k_off))
     values = torch.empty(sum_k, dtype=dtype, device=device)
@@ -555,7 +601,7 @@ def _compress_exchange(state: SparseState, bucket, group, world_size: int, ef: i
                                          int(seg.by_column), int(hashed), int(seed) if hashed else 0,
                                          indices.data_ptr(), values.data_ptr(), ws.data_ptr(), dt,
                                          int(fold14), stream), "arctopk_seg_select")
-        bits_sum = sum_k * (dtype_bits(dtype) + (0 if state.random else 32))
+        bits_sum = sum_k * (value_bits + (0 if state.random else 32))
     elif state.random:
         if state.index_source == "torch":  # the reference's own draw (:20), per tensor in order
             for t, k, ko in zip(tensors, ks, k_off):
@@ -584,7 +630,7 @@ def _compress_exchange(state: SparseState, bucket, group, world_size: int, ef: i
         if state.index_source != "hash":
             N.check(L.arctopk_sparse_gather(xsrc, nt, a_off, a_k, a_ko, indices.data_ptr(),
                                             values.data_ptr(), dt, stream), "arctopk_sparse_gather")
-        bits_sum = sum_k * dtype_bits(dtype)
+        bits_sum = sum_k * value_bits
     else:
         ws_buf = _workspace(state, device, numels)
         rc = N.EINVAL
@@ -600,7 +646,7 @@ def _compress_exchange(state: SparseState, bucket, group, world_size: int, ef: i
             N.check(L.arctopk_topk_select(xsrc, nt, a_off, a_n, a_k, a_ko, indices.data_ptr(),
                                           values.data_ptr(), ws_buf.data_ptr(), dt, int(fold14), stream),
                     "arctopk_topk_select")
-        bits_sum = sum_k * (dtype_bits(dtype) + 32)
+        bits_sum = sum_k * (value_bits + 32)
 
     # the call's selection, for inspection and tests (int32 indices per tensor, concatenated
     # in bucket order at the k offsets; TopK: ascending within a tensor)
@@ -608,11 +654,27 @@ def _compress_exchange(state: SparseState, bucket, group, world_size: int, ef: i
     if on_values is not None:
         on_values(values)
     fused_residual = fold14 and (not state.random or state.index_source == "hash")
-    if ef != N.EF_NONE and not fused_residual:  # residual persistence (:257-267)
+    if wire16:  # the values as they travel, and the residual with what the rounding drops
+        vals16 = torch.empty(sum_k, dtype=torch.bfloat16, device=device)
+        err = state.error_dict[b].data_ptr() if ef != N.EF_NONE else None
+        N.check(L.arctopk_sparse_pack_wire16(values.data_ptr(), err, total, nt, a_off, a_k, a_ko, indices.data_ptr(),
+                                             vals16.data_ptr(), ef, e_decay, stream), "arctopk_sparse_pack_wire16")
+        values = vals16
+    elif ef != N.EF_NONE and not fused_residual:  # residual persistence (:257-267)
         N.check(L.arctopk_sparse_residual(state.error_dict[b].data_ptr(), nt, a_off, a_k, a_ko,
                                           indices.data_ptr(), values.data_ptr(), ef, e_decay, dt, stream),
                 "arctopk_sparse_residual")
     gerr = state.global_error_dict[b].data_ptr() if ef == N.EF21 else None
+
+    def decode(idx, vals, nranks, accumulate):
+        if wire16:
+            N.check(L.arctopk_sparse_decode_wire16(x, total, nt, a_off, a_k, a_ko, sum_k, idx.data_ptr(),
+                                                   vals.data_ptr(), nranks, world_size, accumulate, gerr, g_decay,
+                                                   stream), "arctopk_sparse_decode_wire16")
+        else:
+            N.check(L.arctopk_sparse_decode(x, total, nt, a_off, a_k, a_ko, sum_k, idx.data_ptr(), vals.data_ptr(),
+                                            nranks, world_size, accumulate, gerr, g_decay, dt, stream),
+                    "arctopk_sparse_decode")
 
     if state.random:
         if count_bits:
@@ -621,24 +683,18 @@ def _compress_exchange(state: SparseState, bucket, group, world_size: int, ef: i
             dist.all_reduce(values, group=group, async_op=False)
         # one pass of whole chunks where every tensor's indices ascend (not the column layout)
         ascending = 2 if state.index_source == "hash" and not (seg is not None and seg.by_column) else 0
-        N.check(L.arctopk_sparse_decode(x, total, nt, a_off, a_k, a_ko, sum_k, indices.data_ptr(),
-                                        values.data_ptr(), 1, world_size, ascending, gerr, g_decay, dt,
-                                        stream),
-                "arctopk_sparse_decode")
+        decode(indices, values, 1, ascending)
     else:
         if count_bits:
             state.comm_bits_this_round += (world_size - 1) * world_size * bits_sum
         if world_size > 1:
-            all_vals = torch.empty(world_size * sum_k, dtype=dtype, device=device)
+            all_vals = torch.empty(world_size * sum_k, dtype=values.dtype, device=device)
             all_idx = torch.empty(world_size * sum_k, dtype=torch.int32, device=device)
             _all_gather_flat(all_vals, values, group, world_size)
             _all_gather_flat(all_idx, indices, group, world_size)
         else:  # gathering from one rank is the identity
             all_vals, all_idx = values, indices
-        N.check(L.arctopk_sparse_decode(x, total, nt, a_off, a_k, a_ko, sum_k, all_idx.data_ptr(),
-                                        all_vals.data_ptr(), world_size, world_size,
-                                        3 if seg is not None and seg.by_column else 1, gerr,
-                                        g_decay, dt, stream), "arctopk_sparse_decode")
+        decode(all_idx, all_vals, world_size, 3 if seg is not None and seg.by_column else 1)
 
 
 def _large_batch_ef21(state: SparseState, bucket, c4: bool) -> "torch.futures.Future[torch.Tensor]":

@@ -9,7 +9,9 @@ after compression starts, and ``cal_k`` takes ``(state, tensor)``.
 
 As in ``sparse_hook``, ``SparseState.error_dtype = torch.float32`` (or
 ``ARCTOPK_SPARSE_ERROR_DTYPE=fp32``) keeps a bf16 bucket's EF14 / EF21 residuals in fp32 (DESIGN.md
-section 4g); the ramp runs with it, every call selecting at that call's ratio.
+section 4g); the ramp runs with it, every call selecting at that call's ratio.  So does
+``SparseState.wire_dtype = torch.bfloat16`` (or ``ARCTOPK_SPARSE_WIRE_DTYPE=bf16``), which sends an fp32
+bucket's values as bf16.
 """
 
 import logging

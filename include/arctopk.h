@@ -663,6 +663,62 @@ int arctopk_sparse_decode_mixed21(void* out, void* gE, void* scratch, int64_t nu
                                   const void* vals, int32_t nranks, int32_t world_size, float decay,
                                   void* stream);
 
+/* ---- TopK / RandK baselines: bf16 values on the wire of an fp32 bucket (SparseState.wire_dtype) ---- */
+/*
+ * In this section the bucket (out), the selects' values and the residuals (E, gE) are fp32 and the
+ * payload's values (vals16) are bf16; f and b as above.  Fold and selection are the fp32 path's,
+ * unchanged; these two entries replace arctopk_sparse_residual and arctopk_sparse_decode behind
+ * them.  Tensor i's extent is offsets[i + 1] - offsets[i] (the last one's ends at numel): the
+ * tensors tile [offsets[0], numel) in order.  Both entries check every argument and every batch
+ * of the layout before any device call (host-testable) and return ARCTOPK_EINVAL, with nothing
+ * enqueued, for a null array, ntensors < 1, numel < 1, tensors that do not tile in order, a k
+ * outside [1, extent], or a pointer not aligned to its element.
+ */
+
+/*
+ * Round the selected values to the wire and keep what the rounding drops: for tensor i and
+ * j < ks[i], with p = k_off[i] + j and e = offsets[i] + idx[p],
+ *   vals16[p] = b(values[p])
+ *   EF_NONE : nothing else (E may be NULL)
+ *   EF14    : E[e] := values[p] - f(vals16[p])   (one exact fp32 subtract; a store, so it holds
+ *             whether or not the select has zeroed E[e] already)
+ *   EF21    : E[e] := fma(decay, f(vals16[p]), E[e])   (one rounding)
+ * `values` are the selects' contiguous fp32 values (arctopk_topk_select, arctopk_randk_select,
+ * arctopk_seg_select, their _ef14 forms, or arctopk_sparse_gather).  Other elements of E are
+ * untouched; an index outside its tensor's extent writes vals16 = 0 and nothing else.  One launch
+ * per ARCTOPK_SPARSE_MAX_BATCH tensors; a tensor whose slice of the payload is 16-B aligned goes
+ * in units of 4 (16 B of indices and values in, 8 B out), the rest element by element.
+ * ARCTOPK_EINVAL also for an unknown ef, or EF14 / EF21 with a null E.
+ */
+int arctopk_sparse_pack_wire16(const void* values, void* E, int64_t numel, int32_t ntensors,
+                               const int64_t* offsets, const int64_t* ks, const int64_t* k_off,
+                               const int32_t* idx, void* vals16, int32_t ef, float decay, void* stream);
+
+/*
+ * Decode bf16 payloads into the fp32 bucket (every element written).  `accumulate` has the values
+ * of arctopk_sparse_decode: 0 RandK, any order; 1 TopK, each tensor's idx ascending on every rank;
+ * 2 RandK ascending; 3 TopK, any order.  Per element
+ *   s = 0.0f + f(v_0) + f(v_1) + ...   the ranks' values at that element, added in rank order in
+ *                                      fp32 (TopK: nranks payloads; RandK: the one all-reduced)
+ *   m = s / world_size                 correctly rounded (x 1/ws for a power of two, else a division)
+ *   gE == NULL : out = m  (0 where no rank selected the element)
+ *   gE != NULL : gE := fma(decay, m, gE);  out = gE   (EF21; on every element)
+ * Indices within a payload are distinct; one outside its tensor's extent is skipped.  `vals16` /
+ * `idx` hold nranks consecutive payloads of packed_len entries.
+ * accumulate 1 or 2 with offsets[0] == 0 takes the merged route: one launch per
+ * ARCTOPK_SPARSE_MAX_BATCH tensors in which a block composes a 4096-element chunk of a tensor from
+ * all ranks' slices in LDS, in rank order, and writes it once with mean and gE applied -- no
+ * memset, no read-modify-write of the bucket, no separate divide pass.  Anything else takes the
+ * scattered route: memset, one scatter launch per rank, one finalize pass.  Both give the same bits.
+ * ARCTOPK_EINVAL also for nranks < 1, world_size < 1, packed_len < k_off[i] + ks[i], or accumulate
+ * outside 0..3.
+ */
+int arctopk_sparse_decode_wire16(void* out, int64_t numel, int32_t ntensors, const int64_t* offsets,
+                                 const int64_t* ks, const int64_t* k_off, int64_t packed_len,
+                                 const int32_t* idx, const void* vals16, int32_t nranks,
+                                 int32_t world_size, int32_t accumulate, void* gE, float decay,
+                                 void* stream);
+
 /*
  * Momentum fold of a whole bucket, in place, stream-ordered, one launch per
  * ARCTOPK_SPARSE_MAX_BATCH tensors: for every tensor i,
