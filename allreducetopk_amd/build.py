@@ -28,7 +28,7 @@ LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "libarctopk.so")
 SOURCES = ["plan.hip", "arctopk_kernels.hip", "sparse_kernels.hip", "seg_select.hip", "mselect.hip", "vdraw.hip",
            "projection.cpp", "step.cpp", "exchange.cpp", "wire.hip", "momentum.hip", "mixed_ef.hip", "wire16.hip",
-           "sparse_mixed.hip", "sparse_wire16.hip"]
+           "sparse_mixed.hip"]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wall",
          "-Wno-unused-function"]

@@ -54,8 +54,9 @@ bucket's ``error_dict[b]`` -- and under EF21 ``global_error_dict[b]`` -- in fp32
     decode  EF14: the bf16 decode above | EF21: arctopk_sparse_decode_mixed21: fp32 rank-ordered
             sums, gE := fma(decay, sum / ws, gE), out = b(gE)
 
-with the bf16 wire, the index exchange and the bit accounting of the default path.  The option is
-ignored for fp32 buckets and "noef", and refused with ``large_batch_init`` on a bf16 bucket.
+in the default path's skeleton (``_compress_exchange(mixed=True)``), with its bf16 wire, index
+exchange and bit accounting.  The option is ignored for fp32 buckets and "noef", and refused with
+``large_batch_init`` on a bf16 bucket.
 
 ``SparseState.wire_dtype = torch.bfloat16`` (not in the reference; environment
 default ``ARCTOPK_SPARSE_WIRE_DTYPE=bf16``) sends an fp32 bucket's values as bf16, as
@@ -65,8 +66,7 @@ for bit; behind them such a call runs
 
     pack    arctopk_sparse_pack_wire16  vals16 = b(values); EF14: E[idx] := values - f(vals16), the
             remainder of the rounding | EF21: E[idx] := fma(decay, f(vals16), E[idx])
-            (in place of arctopk_sparse_residual)
-    RandK : all_reduce(vals16) | TopK: all_gather(vals16), all_gather(indices)
+            (in place of arctopk_sparse_residual); the exchange above then carries vals16
     decode  arctopk_sparse_decode_wire16  fp32 rank-ordered sums of f(vals16), / ws, EF21's gE; where
             every tensor's indices ascend (TopK, RandK "hash"; not the column layout) one block
             composes a whole chunk from all ranks in LDS and writes it once
@@ -308,6 +308,23 @@ def _seg_reference_draws(g: _SegGeometry, device) -> torch.Tensor:
     return torch.cat(parts)
 
 
+def _done(state: SparseState, bucket, tensor) -> "torch.futures.Future[torch.Tensor]":
+    """The end of a synchronous hook call: the iteration counter, and a completed Future."""
+    state.maybe_increase_iter(bucket)
+    fut = torch.futures.Future()
+    fut.set_result(tensor)
+    return fut
+
+
+def _reseed(state: SparseState):
+    """RandK's shared reseed, so every rank draws the same indices (:230-235); None for TopK."""
+    if not state.random:
+        return None
+    seed = torch.randint(0, 1_000_000_000, (1,), generator=state.rng).item()
+    torch.manual_seed(seed)
+    return seed
+
+
 def _sparse_hook_impl(state: SparseState, bucket, c4: bool = False) -> "torch.futures.Future[torch.Tensor]":
     if state.use_error_feedback == "ef21" and state.large_batch_init:
         # (sparse_hook.py:172-175, sparse_hook_c4.py:201-204)
@@ -342,11 +359,14 @@ def _sparse_hook_impl(state: SparseState, bucket, c4: bool = False) -> "torch.fu
     # EF21 residual scaling: E += error_decay * C(D), gE += error_decay * out (:265, :296)
     decay = float(state.error_decay)
     wire16 = state._wire16(dtype)  # bf16 values of this fp32 bucket on the wire (wire_dtype)
+    mixed = state._mixed_residual(dtype, ef)  # fp32 residuals under this bf16 bucket (error_dtype)
 
-    if state._mixed_residual(dtype, ef):  # fp32 residuals under this bf16 bucket (error_dtype)
-        return _mixed_call(state, bucket, group, world_size, ef, decay)
-
-    if ef == N.EF14:
+    if ef == N.EF21 and b not in state.error_dict:
+        return _ef21_dense_first_call(state, bucket, group, world_size, mixed)
+    state._fold_in = None  # EF14's err_in where the select folds E itself
+    if mixed:
+        _mixed_fold(state, bucket, ef, stream)
+    elif ef == N.EF14:
         err_in = b in state.error_dict
         if not err_in:
             logger.info("A zero tensor of length %s that represents local error is created.", total)
@@ -356,40 +376,68 @@ def _sparse_hook_impl(state: SparseState, bucket, c4: bool = False) -> "torch.fu
         # from E, and the decode writes the bucket once.  RandK's device draw folds E itself in
         # its write pass (arctopk_randk_select_ef14: its keys never read the data)
         # (and fp32 TopK folds it in its first pass: arctopk_topk_select_ef14)
-        if not _select_folds(state, dtype) or state.sparse_type != "tensor":
+        if _select_folds(state, dtype) and state.sparse_type == "tensor":
+            state._fold_in = int(err_in)
+        else:
             N.check(L.arctopk_ef14_fold(input_tensor.data_ptr(), err.data_ptr(), total, int(err_in),
                                         dt, stream), "arctopk_ef14_fold")
-        state._fold_in = int(err_in)
     elif ef == N.EF21:
-        if b in state.error_dict:
-            err = _residual_on(state.error_dict, b, input_tensor, "error_dict")
-            _residual_on(state.global_error_dict, b, input_tensor, "global_error_dict")
-            N.check(L.arctopk_ef_apply(input_tensor.data_ptr(), err.data_ptr(),
-                                       total, N.EF21, 1, dt, stream), "arctopk_ef_apply")
-        else:  # (:213-226)
-            logger.info("A tensor of length %s that represents local/global error is created.", total)
-            state.error_dict[b] = torch.clone(input_tensor).detach()
-            dist.all_reduce(input_tensor, group=group, async_op=False)
-            input_tensor.div_(world_size)
-            state.global_error_dict[b] = torch.clone(input_tensor).detach()
-            state.maybe_increase_iter(bucket)
-            fut = torch.futures.Future()
-            fut.set_result(input_tensor)
-            return fut
+        err = _residual_on(state.error_dict, b, input_tensor, "error_dict")
+        _residual_on(state.global_error_dict, b, input_tensor, "global_error_dict")
+        N.check(L.arctopk_ef_apply(input_tensor.data_ptr(), err.data_ptr(),
+                                   total, N.EF21, 1, dt, stream), "arctopk_ef_apply")
 
-    if ef != N.EF14 or not _select_folds(state, dtype) or state.sparse_type != "tensor":
-        state._fold_in = None  # (set above only when the select folds E itself)
-    seed = None
-    if state.random:  # shared reseed so every rank draws the same indices (:230-235)
-        seed = torch.randint(0, 1_000_000_000, (1,), generator=state.rng).item()
-        torch.manual_seed(seed)
-    _compress_exchange(state, bucket, group, world_size, ef, state._call_ratio(), seed,
-                       e_decay=decay, g_decay=decay, count_bits=True, ef14_folded=ef == N.EF14, wire16=wire16)
+    _compress_exchange(state, bucket, group, world_size, ef, state._call_ratio(), _reseed(state),
+                       e_decay=decay, g_decay=decay, count_bits=True, ef14_folded=ef == N.EF14, wire16=wire16,
+                       mixed=mixed)
     state.wire16_calls += int(wire16)
-    state.maybe_increase_iter(bucket)
-    fut = torch.futures.Future()
-    fut.set_result(input_tensor)
-    return fut
+    state.mixed_calls += int(mixed)
+    return _done(state, bucket, input_tensor)
+
+
+def _ef21_dense_first_call(state: SparseState, bucket, group, world_size: int,
+                           mixed: bool) -> "torch.futures.Future[torch.Tensor]":
+    """EF21's first call of a bucket (:213-226): E_0 = G, the bucket is all-reduced and averaged,
+    gE_0 = out.  ``mixed``: both are kept as fp32 copies of the bf16 bucket (``error_dtype``)."""
+    input_tensor = bucket.buffer()
+    b = bucket.index()
+
+    def keep(t):  # a copy of its own either way: bf16 -> fp32 converts, so it copies
+        return t.to(torch.float32, copy=True) if mixed else torch.clone(t).detach()
+
+    logger.info("A tensor of length %s that represents local/global error is created.", input_tensor.shape[0])
+    state.error_dict[b] = keep(input_tensor)
+    dist.all_reduce(input_tensor, group=group, async_op=False)
+    input_tensor.div_(world_size)
+    state.global_error_dict[b] = keep(input_tensor)
+    if mixed:
+        state._mixed_buckets.add(int(b))
+    return _done(state, bucket, input_tensor)
+
+
+def _mixed_fold(state: SparseState, bucket, ef: int, stream) -> None:
+    """The EF pre-apply of a bf16 bucket whose residuals are fp32 (``error_dtype``, DESIGN.md section
+    4g): the residuals' bookkeeping and arctopk_sparse_fold_mixed.  EF14: X = f(G) + E then lives in
+    E; EF21: D = f(G) - E lives in the state's fp32 scratch, which the decode reuses for its sums."""
+    input_tensor = bucket.buffer()
+    device = input_tensor.device
+    b = bucket.index()
+    total = input_tensor.shape[0]
+    f32 = torch.float32
+    err_in = b in state.error_dict
+    if not err_in:  # EF14's first call: the fold writes every element
+        logger.info("A zero tensor of length %s that represents local error is created.", total)
+        state.error_dict[b] = torch.empty(total, device=device, dtype=f32)
+        state._mixed_buckets.add(int(b))
+    err = _residual_on(state.error_dict, b, input_tensor, "error_dict", f32)
+    scratch = None
+    if ef == N.EF21:
+        _residual_on(state.global_error_dict, b, input_tensor, "global_error_dict", f32)
+        scratch = state._mixed_scratch
+        if scratch is None or scratch.device != device or scratch.numel() < total:
+            scratch = state._mixed_scratch = torch.empty(total, dtype=f32, device=device)
+    N.check(N.lib().arctopk_sparse_fold_mixed(input_tensor.data_ptr(), err.data_ptr(), N.ptr(scratch), total, ef,
+                                              int(err_in), stream), "arctopk_sparse_fold_mixed")
 
 
 def _select_folds(state: SparseState, dtype) -> bool:
@@ -429,131 +477,60 @@ def _bucket_layout(state: SparseState, input_tensor, tensors, ratio: float):
     return seg, numels, ks, offsets, k_off, acc
 
 
-def _mixed_call(state: SparseState, bucket, group, world_size: int, ef: int,
-                decay: float) -> "torch.futures.Future[torch.Tensor]":
-    """A compressed call of a bf16 bucket whose residuals are fp32 (``error_dtype``, DESIGN.md
-    section 4g), on the caller's stream: fold, the fp32 select (or RandK's draw), pack, the bf16
-    exchange of the default path, decode.  EF21's first call of a bucket is the dense one, as in
-    the default path, with E_0 = f(G) and gE_0 = f(out)."""
-    L = N.lib()
-    input_tensor = bucket.buffer()
-    tensors = bucket.gradients()
-    device = input_tensor.device
-    b = bucket.index()
-    total = input_tensor.shape[0]
-    stream = torch.cuda.current_stream(device).cuda_stream
-    x = input_tensor.data_ptr()
-    f32 = torch.float32
+def _reference_draws(state: SparseState, indices: torch.Tensor, seg, numels, ks, k_off) -> None:
+    """RandK "torch" / "host": the reference's own draws (:20; row / column: _seg_reference_draws)
+    into ``indices``, per tensor in order.  "torch" draws on the bucket's device; "host" (parity
+    mode: the reference run on CPU, sparse_hook_c4.py:20 with CPU tensors, after the reseed at
+    :269-274) draws from the CPU generator in the same order, so that generator is left where the
+    reference leaves it, and copies the draws to the device once."""
+    on_device = state.index_source == "torch"
+    if seg is not None:
+        indices.copy_(_seg_reference_draws(seg, indices.device if on_device else None))
+        return
+    kw = {"device": indices.device} if on_device else {}
+    out = indices if on_device else torch.empty(indices.numel(), dtype=torch.int32)
+    for n, k, ko in zip(numels, ks, k_off):
+        out[ko:ko + k].copy_(torch.randperm(n, **kw)[:k])
+    if not on_device:
+        indices.copy_(out)
 
-    if ef == N.EF21 and b not in state.error_dict:  # (:213-226)
-        logger.info("A tensor of length %s that represents local/global error is created.", total)
-        state.error_dict[b] = input_tensor.float()
-        dist.all_reduce(input_tensor, group=group, async_op=False)
-        input_tensor.div_(world_size)
-        state.global_error_dict[b] = input_tensor.float()
-        state._mixed_buckets.add(int(b))
-        state.maybe_increase_iter(bucket)
-        fut = torch.futures.Future()
-        fut.set_result(input_tensor)
-        return fut
 
-    err_in = b in state.error_dict
-    if not err_in:  # EF14's first call: the fold writes every element
-        logger.info("A zero tensor of length %s that represents local error is created.", total)
-        state.error_dict[b] = torch.empty(total, device=device, dtype=f32)
-        state._mixed_buckets.add(int(b))
-    err = _residual_on(state.error_dict, b, input_tensor, "error_dict", f32)
-    gerr = scratch = None
-    if ef == N.EF21:
-        gerr = _residual_on(state.global_error_dict, b, input_tensor, "global_error_dict", f32)
-        scratch = state._mixed_scratch
-        if scratch is None or scratch.device != device or scratch.numel() < total:
-            scratch = state._mixed_scratch = torch.empty(total, dtype=f32, device=device)
-    # EF14: X = f(G) + E lives in E; EF21: D = f(G) - E lives in the scratch
-    src = err if ef == N.EF14 else scratch
-    N.check(L.arctopk_sparse_fold_mixed(x, err.data_ptr(), N.ptr(scratch), total, ef, int(err_in), stream),
-            "arctopk_sparse_fold_mixed")
+def _seg_workspace(state: SparseState, seg: _SegGeometry, device) -> torch.Tensor:
+    """Segmented-select workspace of this geometry (the state's one workspace, grown, never shrunk)."""
+    ws = state._workspace
+    if ws is None or ws.device != device or ws.numel() < seg.ws_bytes:
+        ws = state._workspace = torch.empty(seg.ws_bytes, dtype=torch.uint8, device=device)
+    return ws
 
-    seed = None
-    if state.random:  # shared reseed so every rank draws the same indices (:230-235)
-        seed = torch.randint(0, 1_000_000_000, (1,), generator=state.rng).item()
-        torch.manual_seed(seed)
-    seg, numels, ks, offsets, k_off, sum_k = _bucket_layout(state, input_tensor, tensors, state._call_ratio())
-    nt = len(tensors)
-    a_off, a_n, a_k, a_ko = (N.i64_array(offsets), N.i64_array(numels), N.i64_array(ks), N.i64_array(k_off))
-    values = torch.empty(sum_k, dtype=torch.bfloat16, device=device)
-    indices = torch.empty(sum_k, dtype=torch.int32, device=device)
-    hashed = state.random and state.index_source == "hash"
-    if state.random and not hashed:  # the reference's own draws, as in the default path
-        if seg is not None:
-            indices.copy_(_seg_reference_draws(seg, device if state.index_source == "torch" else None))
-        elif state.index_source == "torch":
-            for t, k, ko in zip(tensors, ks, k_off):
-                indices[ko:ko + k].copy_(torch.randperm(t.numel(), device=device)[:k])
-        else:
-            host = torch.empty(sum_k, dtype=torch.int32)
-            for t, k, ko in zip(tensors, ks, k_off):
-                host[ko:ko + k].copy_(torch.randperm(t.numel())[:k])
-            indices.copy_(host)
-    elif seg is not None:  # the selects' own fp32 gather goes unused: the pack rounds from src
-        ws = state._workspace
-        if ws is None or ws.device != device or ws.numel() < seg.ws_bytes:
-            ws = state._workspace = torch.empty(seg.ws_bytes, dtype=torch.uint8, device=device)
-        sel_vals = torch.empty(sum_k, dtype=f32, device=device)
-        N.check(L.arctopk_seg_select(src.data_ptr(), nt, a_off, seg.a_rows, seg.a_cols, seg.a_kseg, a_ko,
-                                     int(seg.by_column), int(hashed), int(seed) if hashed else 0,
-                                     indices.data_ptr(), sel_vals.data_ptr(), ws.data_ptr(), N.F32, 0, stream),
-                "arctopk_seg_select")
-    elif hashed:  # indices only: the keys never read the data
-        ws_buf = _workspace(state, device, numels)
-        N.check(L.arctopk_randk_select(None, nt, None, a_n, a_k, a_ko, int(seed), indices.data_ptr(), None,
-                                       ws_buf.data_ptr(), N.F32, 0, stream), "arctopk_randk_select")
-    else:
-        ws_buf = _workspace(state, device, numels)
-        sel_vals = torch.empty(sum_k, dtype=f32, device=device)
-        N.check(L.arctopk_topk_select(src.data_ptr(), nt, a_off, a_n, a_k, a_ko, indices.data_ptr(),
-                                      sel_vals.data_ptr(), ws_buf.data_ptr(), N.F32, 0, stream),
-                "arctopk_topk_select")
-    state.last_indices, state.last_k = indices, ks
-    N.check(L.arctopk_sparse_pack_mixed(src.data_ptr(), err.data_ptr(), total, nt, a_off, a_k, a_ko,
-                                        indices.data_ptr(), values.data_ptr(), ef, decay, stream),
-            "arctopk_sparse_pack_mixed")
 
-    # the exchange of the default path: the values are bf16, the indices int32
-    bits_sum = sum_k * (dtype_bits(torch.bfloat16) + (0 if state.random else 32))
+def _exchange(state: SparseState, group, world_size: int, values, indices, value_bits: int, count_bits: bool,
+              *, hashed: bool, by_column: bool):
+    """The exchange of one compressed call, and its bit accounting (``count_bits``).  RandK:
+    all-reduce of the values, every rank holding the same indices; TopK: all-gather of values and
+    indices.  Returns what the decode reads: (values, indices, nranks, accumulate code).
+    RandK "hash" outside the column layout: every tensor's indices ascend, so the decode may compose
+    whole chunks in one pass (accumulate 2)."""
+    sum_k = indices.numel()
     if state.random:
-        state.comm_bits_this_round += 2 * (world_size - 1) * bits_sum
+        if count_bits:
+            state.comm_bits_this_round += 2 * (world_size - 1) * sum_k * value_bits
         if world_size > 1:
             dist.all_reduce(values, group=group, async_op=False)
-        all_vals, all_idx, nranks = values, indices, 1
-        accumulate = 2 if hashed and not (seg is not None and seg.by_column) else 0
-    else:
-        state.comm_bits_this_round += (world_size - 1) * world_size * bits_sum
-        all_vals, all_idx, nranks = values, indices, world_size
-        if world_size > 1:
-            all_vals = torch.empty(world_size * sum_k, dtype=torch.bfloat16, device=device)
-            all_idx = torch.empty(world_size * sum_k, dtype=torch.int32, device=device)
-            _all_gather_flat(all_vals, values, group, world_size)
-            _all_gather_flat(all_idx, indices, group, world_size)
-        accumulate = 3 if seg is not None and seg.by_column else 1
-    if ef == N.EF14:
-        N.check(L.arctopk_sparse_decode(x, total, nt, a_off, a_k, a_ko, sum_k, all_idx.data_ptr(),
-                                        all_vals.data_ptr(), nranks, world_size, accumulate, None, decay,
-                                        N.BF16, stream), "arctopk_sparse_decode")
-    else:  # the fold's scratch is free again: it takes the fp32 sums
-        N.check(L.arctopk_sparse_decode_mixed21(x, gerr.data_ptr(), scratch.data_ptr(), total, nt, a_off, a_k,
-                                                a_ko, sum_k, all_idx.data_ptr(), all_vals.data_ptr(), nranks,
-                                                world_size, decay, stream), "arctopk_sparse_decode_mixed21")
-    state.mixed_calls += 1
-    state.maybe_increase_iter(bucket)
-    fut = torch.futures.Future()
-    fut.set_result(input_tensor)
-    return fut
+        return values, indices, 1, 2 if hashed and not by_column else 0
+    if count_bits:
+        state.comm_bits_this_round += (world_size - 1) * world_size * sum_k * (value_bits + 32)
+    if world_size > 1:
+        all_vals = torch.empty(world_size * sum_k, dtype=values.dtype, device=values.device)
+        all_idx = torch.empty(world_size * sum_k, dtype=torch.int32, device=values.device)
+        _all_gather_flat(all_vals, values, group, world_size)
+        _all_gather_flat(all_idx, indices, group, world_size)
+        values, indices = all_vals, all_idx  # (gathering from one rank is the identity)
+    return values, indices, world_size, 3 if by_column else 1
 
 
 def _compress_exchange(state: SparseState, bucket, group, world_size: int, ef: int, ratio: float,
                        seed, e_decay: float, g_decay: float, count_bits: bool, on_values=None,
-                       ef14_folded: bool = False, wire16: bool = False) -> None:
+                       ef14_folded: bool = False, wire16: bool = False, mixed: bool = False) -> None:
     """The compressed call after the EF pre-apply, on the caller's stream: select (TopK) or draw
     (RandK) the indices, gather the values, persist the residual (EF14: E[idx] = 0; EF21:
     E[idx] += e_decay * values), exchange (RandK: all-reduce; TopK: all-gather of values and
@@ -565,6 +542,10 @@ def _compress_exchange(state: SparseState, bucket, group, world_size: int, ef: i
     arctopk_sparse_pack_wire16 rounds the values to bf16 and writes the residual in place of
     arctopk_sparse_residual; the values travel and count as 16 bits; arctopk_sparse_decode_wire16
     decodes.
+    ``mixed`` (a bf16 bucket under ``error_dtype=torch.float32``, after _mixed_fold): the selects
+    read fp32 from E (EF14) or the scratch (EF21) and leave E alone; their own fp32 gather goes
+    unused, and the reference draws and "hash" run none: arctopk_sparse_pack_mixed rounds the bf16
+    values from the source and writes the residual; EF21 decodes with arctopk_sparse_decode_mixed21.
     Reference: sparse_hook.py:237-297 (and :363-410 for the large-batch hook)."""
     L = N.lib()
     input_tensor = bucket.buffer()
@@ -578,123 +559,101 @@ def _compress_exchange(state: SparseState, bucket, group, world_size: int, ef: i
     seg, numels, ks, offsets, k_off, sum_k = _bucket_layout(state, input_tensor, tensors, ratio)
     nt = len(tensors)
     fold14 = ef == N.EF14  # the pre-compression bucket lives in E (arctopk_ef14_fold)
+    if seg is not None and fold14 and not ef14_folded:
+        raise RuntimeError("row / column selection under EF14 needs the caller's arctopk_ef14_fold")
+    hashed = state.random and state.index_source == "hash"
+    drawn = state.random and not hashed  # the reference's own draws
     value_bits = 16 if wire16 else dtype_bits(dtype)
     a_off, a_n, a_k, a_ko = (N.i64_array(offsets), N.i64_array(numels), N.i64_array(ks),
                              N.i64_array(k_off))
     values = torch.empty(sum_k, dtype=dtype, device=device)
     indices = torch.empty(sum_k, dtype=torch.int32, device=device)
     x = input_tensor.data_ptr()
-    xsrc = state.error_dict[b].data_ptr() if fold14 else x
-    if seg is not None:
-        if fold14 and not ef14_folded:
-            raise RuntimeError("row / column selection under EF14 needs the caller's arctopk_ef14_fold")
-        hashed = state.random and state.index_source == "hash"
-        if state.random and not hashed:  # the reference's own draws, then the gather
-            indices.copy_(_seg_reference_draws(seg, device if state.index_source == "torch" else None))
-            N.check(L.arctopk_sparse_gather(xsrc, nt, a_off, a_k, a_ko, indices.data_ptr(),
+    err = state.error_dict[b].data_ptr() if ef != N.EF_NONE else None
+    # what a select reads, as which dtype, where it gathers to, whether it zeroes EF14's E[idx]
+    # (:104) in its last pass, and EF14's err_in where it also folds E := G + E (:205) itself
+    if mixed:
+        src = err if fold14 else state._mixed_scratch.data_ptr()
+        sel_vals, sel_dt, zero, fold_in = None, N.F32, 0, None  # (sel_vals: allocated where a select gathers)
+    else:
+        src = err if fold14 else x
+        sel_vals, sel_dt, zero, fold_in = values, dt, int(fold14), state._fold_in if fold14 else None
+    if drawn:
+        _reference_draws(state, indices, seg, numels, ks, k_off)
+        if not mixed:
+            N.check(L.arctopk_sparse_gather(src, nt, a_off, a_k, a_ko, indices.data_ptr(),
                                             values.data_ptr(), dt, stream), "arctopk_sparse_gather")
-        else:  # EF14's `E[indices] = 0` (:104) happens in the select's write pass
-            ws = state._workspace
-            if ws is None or ws.device != device or ws.numel() < seg.ws_bytes:
-                ws = state._workspace = torch.empty(seg.ws_bytes, dtype=torch.uint8, device=device)
-            N.check(L.arctopk_seg_select(xsrc, nt, a_off, seg.a_rows, seg.a_cols, seg.a_kseg, a_ko,
-                                         int(seg.by_column), int(hashed), int(seed) if hashed else 0,
-                                         indices.data_ptr(), values.data_ptr(), ws.data_ptr(), dt,
-                                         int(fold14), stream), "arctopk_seg_select")
-        bits_sum = sum_k * (value_bits + (0 if state.random else 32))
-    elif state.random:
-        if state.index_source == "torch":  # the reference's own draw (:20), per tensor in order
-            for t, k, ko in zip(tensors, ks, k_off):
-                indices[ko:ko + k].copy_(torch.randperm(t.numel(), device=device)[:k])
-        elif state.index_source == "host":
-            # parity mode: the reference run on CPU (sparse_hook_c4.py:20 with CPU tensors, after
-            # the reseed at :269-274) draws from the CPU generator; the same draws, in tensor
-            # order (so the generator is left where the reference leaves it), copied to the GPU
-            host = torch.empty(sum_k, dtype=torch.int32)
-            for t, k, ko in zip(tensors, ks, k_off):
-                host[ko:ko + k].copy_(torch.randperm(t.numel())[:k])
-            indices.copy_(host)
-        elif fold14 and state._fold_in is not None:
-            # "hash" under EF14: the draw, with the fold E := G + E (:205), the gather and
-            # `E[indices] = 0` (:104) all in the select's last pass
-            ws_buf = _workspace(state, device, numels)
-            N.check(L.arctopk_randk_select_ef14(x, state.error_dict[b].data_ptr(), state._fold_in, nt, a_off,
-                                                a_n, a_k, a_ko, int(seed), indices.data_ptr(), values.data_ptr(),
-                                                ws_buf.data_ptr(), dt, stream), "arctopk_randk_select_ef14")
-        else:  # "hash": the k largest keyed-hash keys per tensor, ascending, gathered in the select;
-            # EF14's `E[indices] = 0` (:104) happens in its last pass, as for TopK
-            ws_buf = _workspace(state, device, numels)
-            N.check(L.arctopk_randk_select(xsrc, nt, a_off, a_n, a_k, a_ko, int(seed), indices.data_ptr(),
-                                           values.data_ptr(), ws_buf.data_ptr(), dt, int(fold14), stream),
+    elif seg is not None:
+        ws = _seg_workspace(state, seg, device)
+        if mixed:
+            sel_vals = torch.empty(sum_k, dtype=torch.float32, device=device)
+        N.check(L.arctopk_seg_select(src, nt, a_off, seg.a_rows, seg.a_cols, seg.a_kseg, a_ko,
+                                     int(seg.by_column), int(hashed), int(seed) if hashed else 0,
+                                     indices.data_ptr(), sel_vals.data_ptr(), ws.data_ptr(), sel_dt, zero, stream),
+                "arctopk_seg_select")
+    elif hashed:  # the k largest keyed-hash keys per tensor, ascending, gathered in the select
+        ws_buf = _workspace(state, device, numels)
+        if fold_in is not None:
+            N.check(L.arctopk_randk_select_ef14(x, err, fold_in, nt, a_off, a_n, a_k, a_ko, int(seed),
+                                                indices.data_ptr(), values.data_ptr(), ws_buf.data_ptr(), dt, stream),
+                    "arctopk_randk_select_ef14")
+        elif mixed:  # indices only: the keys never read the data
+            N.check(L.arctopk_randk_select(None, nt, None, a_n, a_k, a_ko, int(seed), indices.data_ptr(), None,
+                                           ws_buf.data_ptr(), N.F32, 0, stream), "arctopk_randk_select")
+        else:
+            N.check(L.arctopk_randk_select(src, nt, a_off, a_n, a_k, a_ko, int(seed), indices.data_ptr(),
+                                           values.data_ptr(), ws_buf.data_ptr(), dt, zero, stream),
                     "arctopk_randk_select")
-        if state.index_source != "hash":
-            N.check(L.arctopk_sparse_gather(xsrc, nt, a_off, a_k, a_ko, indices.data_ptr(),
-                                            values.data_ptr(), dt, stream), "arctopk_sparse_gather")
-        bits_sum = sum_k * value_bits
     else:
         ws_buf = _workspace(state, device, numels)
+        if mixed:
+            sel_vals = torch.empty(sum_k, dtype=torch.float32, device=device)
         rc = N.EINVAL
-        if fold14 and state._fold_in is not None:  # E := G + E (:205) in the select's first pass
-            rc = L.arctopk_topk_select_ef14(x, xsrc, state._fold_in, nt, a_off, a_n, a_k, a_ko,
+        if fold_in is not None:
+            rc = L.arctopk_topk_select_ef14(x, err, fold_in, nt, a_off, a_n, a_k, a_ko,
                                             indices.data_ptr(), values.data_ptr(), ws_buf.data_ptr(), dt, stream)
             if rc == N.EINVAL:  # (a tensor not 16-B aligned / of numel % 4 != 0): fold, then select
-                N.check(L.arctopk_ef14_fold(x, xsrc, total, state._fold_in, dt, stream), "arctopk_ef14_fold")
+                N.check(L.arctopk_ef14_fold(x, err, total, fold_in, dt, stream), "arctopk_ef14_fold")
             else:
                 N.check(rc, "arctopk_topk_select_ef14")
         if rc == N.EINVAL:
-            # EF14: the residual's `E[indices] = 0` (:104) happens in the select's last pass
-            N.check(L.arctopk_topk_select(xsrc, nt, a_off, a_n, a_k, a_ko, indices.data_ptr(),
-                                          values.data_ptr(), ws_buf.data_ptr(), dt, int(fold14), stream),
+            N.check(L.arctopk_topk_select(src, nt, a_off, a_n, a_k, a_ko, indices.data_ptr(),
+                                          sel_vals.data_ptr(), ws_buf.data_ptr(), sel_dt, zero, stream),
                     "arctopk_topk_select")
-        bits_sum = sum_k * (value_bits + 32)
 
     # the call's selection, for inspection and tests (int32 indices per tensor, concatenated
     # in bucket order at the k offsets; TopK: ascending within a tensor)
     state.last_indices, state.last_k = indices, ks
     if on_values is not None:
         on_values(values)
-    fused_residual = fold14 and (not state.random or state.index_source == "hash")
     if wire16:  # the values as they travel, and the residual with what the rounding drops
         vals16 = torch.empty(sum_k, dtype=torch.bfloat16, device=device)
-        err = state.error_dict[b].data_ptr() if ef != N.EF_NONE else None
         N.check(L.arctopk_sparse_pack_wire16(values.data_ptr(), err, total, nt, a_off, a_k, a_ko, indices.data_ptr(),
                                              vals16.data_ptr(), ef, e_decay, stream), "arctopk_sparse_pack_wire16")
         values = vals16
-    elif ef != N.EF_NONE and not fused_residual:  # residual persistence (:257-267)
-        N.check(L.arctopk_sparse_residual(state.error_dict[b].data_ptr(), nt, a_off, a_k, a_ko,
-                                          indices.data_ptr(), values.data_ptr(), ef, e_decay, dt, stream),
-                "arctopk_sparse_residual")
+    elif mixed:
+        N.check(L.arctopk_sparse_pack_mixed(src, err, total, nt, a_off, a_k, a_ko, indices.data_ptr(),
+                                            values.data_ptr(), ef, e_decay, stream), "arctopk_sparse_pack_mixed")
+    elif ef == N.EF21 or (fold14 and drawn):  # residual persistence (:257-267); the selects did EF14's
+        N.check(L.arctopk_sparse_residual(err, nt, a_off, a_k, a_ko, indices.data_ptr(), values.data_ptr(), ef,
+                                          e_decay, dt, stream), "arctopk_sparse_residual")
+
+    by_column = seg is not None and seg.by_column
+    vals, idx, nranks, accumulate = _exchange(state, group, world_size, values, indices, value_bits, count_bits,
+                                              hashed=hashed, by_column=by_column)
     gerr = state.global_error_dict[b].data_ptr() if ef == N.EF21 else None
-
-    def decode(idx, vals, nranks, accumulate):
-        if wire16:
-            N.check(L.arctopk_sparse_decode_wire16(x, total, nt, a_off, a_k, a_ko, sum_k, idx.data_ptr(),
-                                                   vals.data_ptr(), nranks, world_size, accumulate, gerr, g_decay,
-                                                   stream), "arctopk_sparse_decode_wire16")
-        else:
-            N.check(L.arctopk_sparse_decode(x, total, nt, a_off, a_k, a_ko, sum_k, idx.data_ptr(), vals.data_ptr(),
-                                            nranks, world_size, accumulate, gerr, g_decay, dt, stream),
-                    "arctopk_sparse_decode")
-
-    if state.random:
-        if count_bits:
-            state.comm_bits_this_round += 2 * (world_size - 1) * bits_sum
-        if world_size > 1:
-            dist.all_reduce(values, group=group, async_op=False)
-        # one pass of whole chunks where every tensor's indices ascend (not the column layout)
-        ascending = 2 if state.index_source == "hash" and not (seg is not None and seg.by_column) else 0
-        decode(indices, values, 1, ascending)
+    if wire16:
+        N.check(L.arctopk_sparse_decode_wire16(x, total, nt, a_off, a_k, a_ko, sum_k, idx.data_ptr(), vals.data_ptr(),
+                                               nranks, world_size, accumulate, gerr, g_decay, stream),
+                "arctopk_sparse_decode_wire16")
+    elif mixed and ef == N.EF21:  # the fold's scratch is free again: it takes the fp32 sums
+        N.check(L.arctopk_sparse_decode_mixed21(x, gerr, src, total, nt, a_off, a_k, a_ko, sum_k, idx.data_ptr(),
+                                                vals.data_ptr(), nranks, world_size, g_decay, stream),
+                "arctopk_sparse_decode_mixed21")
     else:
-        if count_bits:
-            state.comm_bits_this_round += (world_size - 1) * world_size * bits_sum
-        if world_size > 1:
-            all_vals = torch.empty(world_size * sum_k, dtype=values.dtype, device=device)
-            all_idx = torch.empty(world_size * sum_k, dtype=torch.int32, device=device)
-            _all_gather_flat(all_vals, values, group, world_size)
-            _all_gather_flat(all_idx, indices, group, world_size)
-        else:  # gathering from one rank is the identity
-            all_vals, all_idx = values, indices
-        decode(all_idx, all_vals, world_size, 3 if seg is not None and seg.by_column else 1)
+        N.check(L.arctopk_sparse_decode(x, total, nt, a_off, a_k, a_ko, sum_k, idx.data_ptr(), vals.data_ptr(),
+                                        nranks, world_size, accumulate, gerr, g_decay, dt, stream),
+                "arctopk_sparse_decode")
 
 
 def _large_batch_ef21(state: SparseState, bucket, c4: bool) -> "torch.futures.Future[torch.Tensor]":
@@ -731,10 +690,7 @@ def _large_batch_ef21(state: SparseState, bucket, c4: bool) -> "torch.futures.Fu
         dist.all_reduce(input_tensor, group=group, async_op=False)
         input_tensor.div_(world_size)
         state.global_error_dict[b].add_(input_tensor, alpha=1.0)
-        state.maybe_increase_iter(bucket)
-        fut = torch.futures.Future()
-        fut.set_result(input_tensor)
-        return fut
+        return _done(state, bucket, input_tensor)
     if state.iter == state.start_compress_iter:
         state.error_dict[b].div_(state.start_compress_iter - 1)
         state.global_error_dict[b].div_(state.start_compress_iter - 1)
@@ -745,10 +701,7 @@ def _large_batch_ef21(state: SparseState, bucket, c4: bool) -> "torch.futures.Fu
     stream = torch.cuda.current_stream(input_tensor.device).cuda_stream
     N.check(L.arctopk_ef_apply(input_tensor.data_ptr(), err.data_ptr(), total, N.EF21, 1,
                                N.DTYPE_CODE[input_tensor.dtype], stream), "arctopk_ef_apply")
-    seed = None
-    if state.random:
-        seed = torch.randint(0, 1_000_000_000, (1,), generator=state.rng).item()
-        torch.manual_seed(seed)
+    seed = _reseed(state)
     if c4:
         raise AttributeError("'Tensor' object has no attribute 'get_current_compress_ratio'")
     log_diff = bucket.is_last() and dist.get_rank() == 0 and logger.isEnabledFor(logging.INFO)
@@ -762,10 +715,7 @@ def _large_batch_ef21(state: SparseState, bucket, c4: bool) -> "torch.futures.Fu
                        on_values=vals_seen.append if log_diff else None)
     if log_diff:
         logger.info(f"Rank[{dist.get_rank()}] Iter[{state.iter}], Diff error{sq[0](vals_seen[0])}")
-    state.maybe_increase_iter(bucket)
-    fut = torch.futures.Future()
-    fut.set_result(input_tensor)
-    return fut
+    return _done(state, bucket, input_tensor)
 
 
 def _all_gather_flat(out: torch.Tensor, inp: torch.Tensor, group, world_size: int) -> None:

@@ -16,8 +16,11 @@
 
 #include "common.h"
 #include "mselect.h"
+#include "sparse_common.h"
 
 namespace {
+
+using arctopk::wave_lower_bound;
 
 constexpr int kB = ARCTOPK_SPARSE_MAX_BATCH;
 
@@ -26,7 +29,6 @@ struct SparseBatch {
     int64_t n[kB];
     int64_t k[kB];
     int64_t koff[kB];
-    int32_t nt;
 };
 
 
@@ -88,25 +90,6 @@ __global__ void __launch_bounds__(256) k_scatter(SparseBatch b, T* __restrict__ 
 // scattered pass.
 constexpr int kDecChunk = 4096;
 
-// first position in a[lo, hi) with a[p] >= target (a ascending), one wave
-__device__ __forceinline__ int64_t wave_lower_bound(const int32_t* __restrict__ a, int64_t lo, int64_t hi,
-                                                    int32_t target) {
-    const int lane = threadIdx.x & 63;
-    while (hi - lo > 64) {
-        const int64_t step = (hi - lo + 63) / 64;
-        const int64_t p = lo + (int64_t)lane * step;
-        const bool pred = p < hi && a[p] < target;
-        const int c = __popcll(__ballot(pred));
-        if (c == 0) return lo;
-        const int64_t nlo = lo + (int64_t)(c - 1) * step + 1;
-        const int64_t phi = lo + (int64_t)c * step;
-        hi = phi < hi ? phi : hi;
-        lo = nlo;
-    }
-    const int64_t p = lo + lane;
-    return lo + __popcll(__ballot(p < hi && a[p] < target));
-}
-
 template <typename T, bool DIV>
 __global__ void __launch_bounds__(256) k_scatter_first(SparseBatch b, T* __restrict__ out,
                                                        const int32_t* __restrict__ idx,
@@ -157,7 +140,6 @@ __global__ void __launch_bounds__(256) k_div_gE(T* __restrict__ out, T* __restri
 int fill_batch(SparseBatch& b, int32_t first, int32_t count, const int64_t* offsets,
                const int64_t* numels, const int64_t* ks, const int64_t* k_off, int64_t& maxn,
                int64_t& maxk) {
-    b.nt = count;
     maxn = maxk = 0;
     for (int i = 0; i < count; ++i) {
         b.off[i] = offsets ? offsets[first + i] : 0;

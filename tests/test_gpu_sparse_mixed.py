@@ -172,7 +172,7 @@ def test_pack_checks_every_index_against_its_tensor():
 
 
 @pytest.mark.parametrize("nranks,ws,decay", [(1, 1, 1.0), (1, 2, 1.0), (1, 3, 0.7), (2, 2, 0.7), (2, 3, 1.0)])
-@pytest.mark.parametrize("name", ["mix", "aligned", "tail"])
+@pytest.mark.parametrize("name", ["mix", "aligned", "tail", "many"])
 def test_decode_mixed21_phase(name, nranks, ws, decay):
     shapes = SETS[name]
     _, gE0, g = _inputs(shapes, 3)
@@ -191,6 +191,35 @@ def test_decode_mixed21_phase(name, nranks, ws, decay):
     N.check(N.lib().arctopk_sparse_decode_mixed21(out_d.data_ptr(), gE_d.data_ptr(), scr_d.data_ptr(), n, len(shapes),
                                                   N.i64_array(offs), N.i64_array(ks), N.i64_array(koff), sum(ks),
                                                   idx_d.data_ptr(), vals_d.data_ptr(), nranks, ws, decay, _stream()),
+            "arctopk_sparse_decode_mixed21")
+    torch.cuda.synchronize()
+    assert_bitwise(gE_d.view(torch.int32), want_gE.view(torch.int32), "gE bits")
+    assert_bitwise(out_d, want_out, "out")
+    assert _intact(obuf, out_d) and _intact(gbuf, gE_d) and _intact(sbuf, scr_d)
+
+
+def test_decode_mixed21_skips_an_index_outside_its_tensor():
+    """-1, a tensor's numel and INT32_MAX among valid indices, in both ranks' payloads: those entries
+    add nothing, every other element is what the valid entries alone give, the guards stay intact."""
+    shapes, ks = [[8], [8]], [3, 4]
+    i32 = torch.int32
+    idx = [[torch.tensor([-1, 2, 5], dtype=i32), torch.tensor([0, 3, 8, 2 ** 31 - 1], dtype=i32)],
+           [torch.tensor([7, -1, 8], dtype=i32), torch.tensor([8, 1, 3, -5], dtype=i32)]]
+    vals = [torch.arange(1.0, 8.0).to(BF16), torch.arange(8.0, 15.0).to(BF16)]
+    valid_idx = [[torch.tensor([2, 5], dtype=i32), torch.tensor([0, 3], dtype=i32)],
+                 [torch.tensor([7], dtype=i32), torch.tensor([1, 3], dtype=i32)]]
+    valid_vals = [torch.tensor([2.0, 3.0, 4.0, 5.0]).to(BF16), torch.tensor([8.0, 12.0, 13.0]).to(BF16)]
+    gE0 = torch.arange(16.0) * 0.37 - 1.0
+    want_out, want_gE = SM.decode21(valid_vals, valid_idx, shapes, 2, gE0, 0.7)
+    assert want_gE[11] != gE0[11] and want_gE[4] == gE0[4] and want_gE[15] == gE0[15]  # 3: both ranks; 4, 15: none
+    obuf, out_d = _guarded(torch.full((16,), 5.0, dtype=BF16))
+    gbuf, gE_d = _guarded(gE0)
+    sbuf, scr_d = _guarded(torch.full((16,), 9.0))
+    idx_d = torch.cat([torch.cat(ix) for ix in idx]).to(DEV)
+    vals_d = torch.cat(vals).to(DEV)
+    N.check(N.lib().arctopk_sparse_decode_mixed21(out_d.data_ptr(), gE_d.data_ptr(), scr_d.data_ptr(), 16, 2,
+                                                  N.i64_array([0, 8]), N.i64_array(ks), N.i64_array([0, 3]), 7,
+                                                  idx_d.data_ptr(), vals_d.data_ptr(), 2, 2, 0.7, _stream()),
             "arctopk_sparse_decode_mixed21")
     torch.cuda.synchronize()
     assert_bitwise(gE_d.view(torch.int32), want_gE.view(torch.int32), "gE bits")
@@ -246,9 +275,10 @@ def test_topk_ties_resolve_lowest_index_first():
 HOOK_CASES = [(kind, source, ef, name, "tensor", False)
               for name in ("mix", "many") for ef in ("ef14", "ef21")
               for kind, source in (("topk", "host"), ("randk", "host"), ("randk", "torch"), ("randk", "hash"))]
-HOOK_CASES += [("topk", "host", "ef14", "mix2d", "row", False), ("topk", "host", "ef21", "mix2d", "column", False),
-               ("randk", "hash", "ef21", "mix2d", "row", False), ("randk", "host", "ef14", "mix2d", "column", False),
-               ("topk", "host", "ef14", "mix", "tensor", True), ("randk", "hash", "ef21", "mix", "tensor", True),
+HOOK_CASES += [(kind, source, ef, "mix2d", sparse_type, False)
+               for kind, source in (("topk", "host"), ("randk", "host"), ("randk", "hash"))
+               for ef in ("ef14", "ef21") for sparse_type in ("row", "column")]
+HOOK_CASES += [("topk", "host", "ef14", "mix", "tensor", True), ("randk", "hash", "ef21", "mix", "tensor", True),
                ("topk", "host", "ef21", "mix", "tensor", True)]
 
 

@@ -1,5 +1,5 @@
 """bf16 values on the wire of an fp32 bucket for the TopK / RandK hooks (``SparseState.wire_dtype``,
-DESIGN.md section 4h) on the GPU: the two entries of csrc/sparse_wire16.hip phase by phase (both
+DESIGN.md section 4h) on the GPU: the two wire entries of csrc/sparse_mixed.hip phase by phase (both
 decode routes), the hooks at world size 1 and on two ranks, refusals and checkpoints -- everything
 bit for bit against the restatement in tests/sparse_wire16_oracle.py."""
 import os
