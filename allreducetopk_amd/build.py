@@ -28,10 +28,14 @@ LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "libarctopk.so")
 SOURCES = ["plan.hip", "arctopk_kernels.hip", "sparse_kernels.hip", "seg_select.hip", "mselect.hip", "vdraw.hip",
            "projection.cpp", "step.cpp", "exchange.cpp", "wire.hip", "momentum.hip", "mixed_ef.hip", "wire16.hip",
-           "sparse_mixed.hip"]
+           "sparse_mixed.hip", "sparse_idx16.hip"]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wall",
          "-Wno-unused-function"]
+# per-source flags on top of FLAGS: new files keep the compiler from choosing the packed fp32
+# instructions (v_pk_add_f32, v_pk_mul_f32, v_pk_fma_f32); the older files' machine code stays as it is
+NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+SOURCE_FLAGS = {"sparse_idx16.hip": NO_PACKED_FP32}
 HASH_RE = re.compile(rb"src:([0-9a-f]{16})")
 
 
@@ -53,7 +57,8 @@ def source_hash(defines=()) -> str:
             h.update(fh.read())
     with open(os.path.join(INCLUDE, "arctopk.h"), "rb") as fh:
         h.update(fh.read())
-    h.update(" ".join([ARCH, *FLAGS, *sorted(defines)]).encode())
+    per_source = [f"{k}:{' '.join(v)}" for k, v in sorted(SOURCE_FLAGS.items())]
+    h.update(" ".join([ARCH, *FLAGS, *sorted(defines), *per_source]).encode())
     return h.hexdigest()[:16]
 
 
@@ -86,8 +91,8 @@ def build(force: bool = False, verbose: bool = False, out: str = LIB, defines=()
     os.makedirs(objdir, exist_ok=True)
     objs = [os.path.join(objdir, os.path.basename(s_) + ".o") for s_ in srcs]
     # one compiler process per source (the kernels file dominates; the others overlap it)
-    cmds = [[hipcc(), *[f for f in common if f != "-shared"], "-c", s_, "-o", o]
-            for s_, o in zip(srcs, objs)]
+    cmds = [[hipcc(), *[f for f in common if f != "-shared"], *SOURCE_FLAGS.get(os.path.basename(s_), []),
+             "-c", s_, "-o", o] for s_, o in zip(srcs, objs)]
     if verbose:
         for c in cmds:
             print(" ".join(c), file=sys.stderr)

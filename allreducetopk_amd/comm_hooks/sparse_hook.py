@@ -74,6 +74,22 @@ for bit; behind them such a call runs
 also at world size 1, so one GPU produces what a rank of N would.  Residuals stay plain fp32.  The
 option is ignored for bf16 buckets (their wire is bf16 already), in the dense warm-up calls and in
 EF21's dense first call of a bucket, and refused with ``large_batch_init`` on an fp32 bucket.
+
+``SparseState.index_wire = "idx16"`` (not in the reference; environment
+default ``ARCTOPK_SPARSE_INDEX_WIRE=idx16``) sends TopK's indices as 16-bit offsets into the
+65,536-element blocks of their tensor plus one int32 per block (the format: include/arctopk.h): half
+of the int32 indices' bytes at any ratio.  Selection, residuals and values are untouched (with or
+without ``wire_dtype`` and ``error_dtype``); behind them such a call runs
+
+    pack    arctopk_sparse_idx16_pack   the int32 selection -> one byte buffer; all_gather(values),
+            all_gather(bytes) in place of all_gather(indices)
+    decode  an fp32 bucket (fp32 or bf16 values): arctopk_sparse_decode_idx16 reads the format and
+            writes the bucket in one pass | a bf16 bucket: arctopk_sparse_idx16_unpack, then the
+            decode above
+
+also at world size 1.  ``sparse_type`` "tensor" and "row" only: "column" (whose indices do not
+ascend) and ``large_batch_init`` raise ValueError; RandK (no index on the wire), the dense warm-up
+calls and EF21's dense first call ignore the option.
 """
 
 import logging
@@ -178,6 +194,13 @@ class SparseState(HookState):
             raise ValueError(f"ARCTOPK_SPARSE_WIRE_DTYPE must be 'bf16' (or unset), got {env!r}")
         self.wire_dtype = torch.bfloat16 if env == "bf16" else None
         self.wire16_calls = 0  # compressed calls that sent bf16 values of an fp32 bucket
+        # Index wire (not in the reference): None sends TopK's indices as int32;
+        # "idx16" as 16-bit block offsets and a table of block starts.  Ignored by RandK.
+        env = os.environ.get("ARCTOPK_SPARSE_INDEX_WIRE", "")
+        if env not in ("", "idx16"):
+            raise ValueError(f"ARCTOPK_SPARSE_INDEX_WIRE must be 'idx16' (or unset), got {env!r}")
+        self.index_wire = "idx16" if env == "idx16" else None
+        self.idx16_calls = 0  # compressed calls that sent their indices so
 
     # ratio of this call; the c4 variant overrides (gradual compression)
     def _call_ratio(self) -> float:
@@ -203,8 +226,23 @@ class SparseState(HookState):
             raise ValueError(f"wire_dtype must be None or torch.bfloat16, got {wd!r}")
         return wd is not None and bucket_dtype == torch.float32
 
+    def _idx16(self) -> bool:
+        """Whether this call sends its indices as 16-bit block offsets.  ValueError for an
+        ``index_wire`` other than None / "idx16", and for the column layout, whose indices do not
+        ascend; ignored by RandK, which sends no index."""
+        iw = self.index_wire
+        if iw is not None and iw != "idx16":
+            raise ValueError(f"index_wire must be None or 'idx16', got {iw!r}")
+        if iw is None or self.random:
+            return False
+        if self.sparse_type == "column":
+            raise ValueError("index_wire='idx16' does not run with sparse_type='column': the format needs "
+                             "every tensor's indices ascending")
+        return True
+
     def state_dict(self) -> dict:
         out = super().state_dict()
+        out["index_wire"] = self.index_wire  # for information: nothing about the residuals changes
         # for information: the residuals are plain fp32 either way, so loading needs no rule
         out["wire_dtype"] = "bf16" if self.wire_dtype is torch.bfloat16 else None
         # the residual dtype option, and the buckets whose fp32 residuals belong to a bf16 bucket
@@ -336,6 +374,9 @@ def _sparse_hook_impl(state: SparseState, bucket, c4: bool = False) -> "torch.fu
         if state._wire16(bucket.buffer().dtype):
             raise ValueError("wire_dtype=torch.bfloat16 does not run with large_batch_init: that hook "
                              "keeps a float32 bucket's float32 wire")
+        if state._idx16():
+            raise ValueError("index_wire='idx16' does not run with large_batch_init: that hook keeps the "
+                             "int32 index wire")
         return _large_batch_ef21(state, bucket, c4)
     state.maybe_accumulate_momentum_on_bucket(bucket)
     group = state.process_group if state.process_group is not None else dist.group.WORLD
@@ -360,6 +401,7 @@ def _sparse_hook_impl(state: SparseState, bucket, c4: bool = False) -> "torch.fu
     decay = float(state.error_decay)
     wire16 = state._wire16(dtype)  # bf16 values of this fp32 bucket on the wire (wire_dtype)
     mixed = state._mixed_residual(dtype, ef)  # fp32 residuals under this bf16 bucket (error_dtype)
+    idx16 = state._idx16()  # TopK's indices as 16-bit block offsets on the wire (index_wire)
 
     if ef == N.EF21 and b not in state.error_dict:
         return _ef21_dense_first_call(state, bucket, group, world_size, mixed)
@@ -389,7 +431,8 @@ def _sparse_hook_impl(state: SparseState, bucket, c4: bool = False) -> "torch.fu
 
     _compress_exchange(state, bucket, group, world_size, ef, state._call_ratio(), _reseed(state),
                        e_decay=decay, g_decay=decay, count_bits=True, ef14_folded=ef == N.EF14, wire16=wire16,
-                       mixed=mixed)
+                       mixed=mixed, idx16=idx16)
+    state.idx16_calls += int(idx16)
     state.wire16_calls += int(wire16)
     state.mixed_calls += int(mixed)
     return _done(state, bucket, input_tensor)
@@ -504,12 +547,16 @@ def _seg_workspace(state: SparseState, seg: _SegGeometry, device) -> torch.Tenso
 
 
 def _exchange(state: SparseState, group, world_size: int, values, indices, value_bits: int, count_bits: bool,
-              *, hashed: bool, by_column: bool):
+              *, hashed: bool, by_column: bool, idx16=None):
     """The exchange of one compressed call, and its bit accounting (``count_bits``).  RandK:
     all-reduce of the values, every rank holding the same indices; TopK: all-gather of values and
     indices.  Returns what the decode reads: (values, indices, nranks, accumulate code).
     RandK "hash" outside the column layout: every tensor's indices ascend, so the decode may compose
-    whole chunks in one pass (accumulate 2)."""
+    whole chunks in one pass (accumulate 2).
+    ``idx16`` (TopK under ``index_wire="idx16"``): (this rank's packed index bytes, the layout's
+    number of 65,536-element blocks); the byte buffers are gathered in place of the indices and
+    returned in their place.  Counted are the format's information bits, 16 per index and 32 per
+    block; its padding to 16 B (at most 30 bytes per rank) is not."""
     sum_k = indices.numel()
     if state.random:
         if count_bits:
@@ -517,11 +564,16 @@ def _exchange(state: SparseState, group, world_size: int, values, indices, value
         if world_size > 1:
             dist.all_reduce(values, group=group, async_op=False)
         return values, indices, 1, 2 if hashed and not by_column else 0
+    if idx16 is not None:
+        indices, blocks = idx16
+        index_bits = sum_k * 16 + blocks * 32
+    else:
+        index_bits = sum_k * 32
     if count_bits:
-        state.comm_bits_this_round += (world_size - 1) * world_size * sum_k * (value_bits + 32)
+        state.comm_bits_this_round += (world_size - 1) * world_size * (sum_k * value_bits + index_bits)
     if world_size > 1:
         all_vals = torch.empty(world_size * sum_k, dtype=values.dtype, device=values.device)
-        all_idx = torch.empty(world_size * sum_k, dtype=torch.int32, device=values.device)
+        all_idx = torch.empty(world_size * indices.numel(), dtype=indices.dtype, device=values.device)
         _all_gather_flat(all_vals, values, group, world_size)
         _all_gather_flat(all_idx, indices, group, world_size)
         values, indices = all_vals, all_idx  # (gathering from one rank is the identity)
@@ -530,7 +582,8 @@ def _exchange(state: SparseState, group, world_size: int, values, indices, value
 
 def _compress_exchange(state: SparseState, bucket, group, world_size: int, ef: int, ratio: float,
                        seed, e_decay: float, g_decay: float, count_bits: bool, on_values=None,
-                       ef14_folded: bool = False, wire16: bool = False, mixed: bool = False) -> None:
+                       ef14_folded: bool = False, wire16: bool = False, mixed: bool = False,
+                       idx16: bool = False) -> None:
     """The compressed call after the EF pre-apply, on the caller's stream: select (TopK) or draw
     (RandK) the indices, gather the values, persist the residual (EF14: E[idx] = 0; EF21:
     E[idx] += e_decay * values), exchange (RandK: all-reduce; TopK: all-gather of values and
@@ -546,6 +599,10 @@ def _compress_exchange(state: SparseState, bucket, group, world_size: int, ef: i
     read fp32 from E (EF14) or the scratch (EF21) and leave E alone; their own fp32 gather goes
     unused, and the reference draws and "hash" run none: arctopk_sparse_pack_mixed rounds the bf16
     values from the source and writes the residual; EF21 decodes with arctopk_sparse_decode_mixed21.
+    ``idx16`` (TopK under ``index_wire="idx16"``, not the column layout): behind all of the above
+    arctopk_sparse_idx16_pack turns the int32 selection into the byte buffer that travels in its
+    place; an fp32 bucket decodes it with arctopk_sparse_decode_idx16 (fp32 or bf16 values), anything
+    else expands it with arctopk_sparse_idx16_unpack and decodes as before.
     Reference: sparse_hook.py:237-297 (and :363-410 for the large-batch hook)."""
     L = N.lib()
     input_tensor = bucket.buffer()
@@ -639,9 +696,30 @@ def _compress_exchange(state: SparseState, bucket, group, world_size: int, ef: i
                                           e_decay, dt, stream), "arctopk_sparse_residual")
 
     by_column = seg is not None and seg.by_column
+    packed = None
+    if idx16:  # the indices as they travel
+        wire_bytes = int(L.arctopk_sparse_idx16_bytes(total, nt, a_off, a_k, a_ko))
+        if wire_bytes < 0:
+            N.check(-wire_bytes, "arctopk_sparse_idx16_bytes")
+        wire = torch.empty(wire_bytes, dtype=torch.uint8, device=device)
+        N.check(L.arctopk_sparse_idx16_pack(total, nt, a_off, a_k, a_ko, indices.data_ptr(), wire.data_ptr(), stream),
+                "arctopk_sparse_idx16_pack")
+        packed = (wire, sum((n + 65535) // 65536 for n in numels))
     vals, idx, nranks, accumulate = _exchange(state, group, world_size, values, indices, value_bits, count_bits,
-                                              hashed=hashed, by_column=by_column)
+                                              hashed=hashed, by_column=by_column, idx16=packed)
     gerr = state.global_error_dict[b].data_ptr() if ef == N.EF21 else None
+    if idx16:
+        if dtype == torch.float32:  # one pass from the format into the bucket
+            rc = L.arctopk_sparse_decode_idx16(x, total, nt, a_off, a_k, a_ko, sum_k, idx.data_ptr(), wire_bytes,
+                                               vals.data_ptr(), N.BF16 if wire16 else N.F32, nranks, world_size,
+                                               gerr, g_decay, stream)
+            if rc != N.EINVAL:  # (a layout that does not start at 0: as a bf16 bucket)
+                N.check(rc, "arctopk_sparse_decode_idx16")
+                return
+        unpacked = torch.empty(nranks * sum_k, dtype=torch.int32, device=device)
+        N.check(L.arctopk_sparse_idx16_unpack(total, nt, a_off, a_k, a_ko, sum_k, idx.data_ptr(), wire_bytes, nranks,
+                                              unpacked.data_ptr(), stream), "arctopk_sparse_idx16_unpack")
+        idx = unpacked
     if wire16:
         N.check(L.arctopk_sparse_decode_wire16(x, total, nt, a_off, a_k, a_ko, sum_k, idx.data_ptr(), vals.data_ptr(),
                                                nranks, world_size, accumulate, gerr, g_decay, stream),

@@ -47,13 +47,6 @@ constexpr int kStreamGrid = 4096;  // blocks of a whole-bucket stream at most
 typedef int32_t vi4_t __attribute__((ext_vector_type(4)));
 typedef uint32_t vu2_t __attribute__((ext_vector_type(2)));
 
-struct MixedBatch {
-    int64_t off[kB];
-    int64_t n[kB];
-    int64_t k[kB];
-    int64_t koff[kB];
-};
-
 // ---- fold (error_dtype) --------------------------------------------------------------------
 // the 8 bf16 of a 16-B unit as two fp32 quads
 __device__ __forceinline__ void unpack8(u4_t w, vf4_t& a, vf4_t& b) {
@@ -406,39 +399,7 @@ inline int stream_grid(int64_t work_items, int per_block) {
 
 inline int gather_grid(int64_t work) { return (int)std::max<int64_t>(1, std::min<int64_t>(2048, (work + 255) / 256)); }
 
-// Every batch of the layout, checked, before anything is launched: tensor i's extent is
-// offsets[i + 1] - offsets[i] (the last one's ends at numel), the tensors tile [offsets[0], numel) in
-// order, 1 <= k <= extent and the payload slices lie in [0, packed_len) (packed_len < 0: not
-// checked).  ARCTOPK_EINVAL otherwise.
-struct Batches {
-    std::vector<MixedBatch> b;
-    std::vector<int64_t> maxk, maxn;
-    int32_t nt;
-    int count(size_t q) const { return std::min<int32_t>(kB, nt - (int32_t)q * kB); }  // tensors of batch q
-};
-
-int fill_batches(Batches& bs, int32_t nt, int64_t numel, const int64_t* offsets, const int64_t* ks,
-                 const int64_t* k_off, int64_t packed_len) {
-    bs.nt = nt;
-    bs.b.resize((nt + kB - 1) / kB);
-    bs.maxk.assign(bs.b.size(), 0);
-    bs.maxn.assign(bs.b.size(), 0);
-    for (int32_t t = 0; t < nt; ++t) {
-        MixedBatch& b = bs.b[t / kB];
-        const int i = t % kB;
-        const int64_t end = t + 1 < nt ? offsets[t + 1] : numel;
-        b.off[i] = offsets[t];
-        b.n[i] = end - offsets[t];
-        b.k[i] = ks[t];
-        b.koff[i] = k_off[t];
-        if (offsets[t] < 0 || end > numel || b.n[i] < 1 || b.n[i] >= (1ll << 31)) return ARCTOPK_EINVAL;
-        if (b.k[i] < 1 || b.k[i] > b.n[i] || b.koff[i] < 0) return ARCTOPK_EINVAL;
-        if (packed_len >= 0 && b.koff[i] + b.k[i] > packed_len) return ARCTOPK_EINVAL;
-        bs.maxk[t / kB] = std::max(bs.maxk[t / kB], b.k[i]);
-        bs.maxn[t / kB] = std::max(bs.maxn[t / kB], b.n[i]);
-    }
-    return 0;
-}
+// (MixedBatch, Batches and fill_batches, the checked layout batch by batch: sparse_common.h)
 
 // every rank's payload into the (zeroed) sums, in rank order, batch by batch
 int scatter_ranks(const Batches& bs, float* sums, const int32_t* idx, const uint16_t* vals, int32_t nranks,

@@ -719,6 +719,81 @@ int arctopk_sparse_decode_wire16(void* out, int64_t numel, int32_t ntensors, con
                                  int32_t world_size, int32_t accumulate, void* gE, float decay,
                                  void* stream);
 
+/* ---- TopK baseline: indices as 16-bit block offsets on the wire (SparseState.index_wire = "idx16") ---- */
+/*
+ * Wire format "idx16".  A layout is numel, ntensors, offsets, ks, k_off as in the section above:
+ * tensor i's extent is n_i = offsets[i + 1] - offsets[i] (the last one's ends at numel), its ks[i]
+ * indices sit at k_off[i] in the payload, tensor-relative and ascending (arctopk_topk_select,
+ * arctopk_seg_select with by_column = 0).  With
+ *   packed_len = k_off[last] + ks[last],  nb_i = ceil(n_i / 65536),  tb_i = sum of nb_t over t < i
+ * one rank's index payload is one byte buffer:
+ *   bytes [0, 2 * packed_len)  uint16 lo16[p] = idx[p] & 0xFFFF
+ *   zero padding to the next multiple of 16
+ *   int32 T[sum of nb_i]       T[tb_i + b] = the number of tensor i's indices below b * 65536; so
+ *                              T[tb_i] = 0 and block b's slice of the tensor's entries is
+ *                              [T[tb_i + b], T[tb_i + b + 1]), the last block's ending at ks[i]
+ *   zero padding to a multiple of 16
+ * Entry j of block b of tensor i is the index b << 16 | lo16[k_off[i] + j].  The size depends on the
+ * layout alone: 16 bits per index and 32 per block, half of int32 at any ratio.
+ * Every entry below checks its layout before any device call (host-testable) and returns
+ * ARCTOPK_EINVAL, with nothing enqueued, for what the section above refuses: a null array,
+ * ntensors < 1, numel < 1, tensors that do not tile [offsets[0], numel) in order, a k outside
+ * [1, extent], or a pointer not aligned to its element (the byte buffer: to 4 B).
+ */
+
+/* Bytes of one rank's payload; -ARCTOPK_EINVAL for a layout as above. */
+int64_t arctopk_sparse_idx16_bytes(int64_t numel, int32_t ntensors, const int64_t* offsets,
+                                   const int64_t* ks, const int64_t* k_off);
+
+/*
+ * idx (packed_len int32, each tensor's ascending) -> wire (arctopk_sparse_idx16_bytes bytes, every
+ * byte written, padding included).  One launch per ARCTOPK_SPARSE_MAX_BATCH tensors, one pass over
+ * the indices: a tensor whose slices of idx and of lo16 are 16-B aligned goes in units of 8 (2 x 16
+ * B in, 16 B out, nontemporal, several units' loads before the first store), the ks % 8 rest and
+ * other tensors element by element.  The thread that holds entry j also holds entry j - 1's block
+ * number and writes the table entries of the blocks between the two (entry 0: from block 0; the
+ * last entry: every later block = ks), so no second pass and no atomic.  Indices that do not ascend
+ * give an unspecified table; every table store is clamped to the tensor's blocks.
+ */
+int arctopk_sparse_idx16_pack(int64_t numel, int32_t ntensors, const int64_t* offsets,
+                              const int64_t* ks, const int64_t* k_off, const int32_t* idx, void* wire,
+                              void* stream);
+
+/*
+ * wire (nranks payloads, wire_stride_bytes apart) -> idx_out (nranks x packed_len int32): the
+ * format's inverse, for the decodes that read int32 indices.  Grid (block of a tensor, tensor,
+ * rank); table entries are clamped to [0, ks] and ordered, so a payload that holds anything writes
+ * inside idx_out only (entries no slice covers are left as they were).
+ * ARCTOPK_EINVAL also for nranks outside [1, 65535], packed_len other than the layout's, or a
+ * stride below the payload's bytes or not a multiple of 4.
+ */
+int arctopk_sparse_idx16_unpack(int64_t numel, int32_t ntensors, const int64_t* offsets,
+                                const int64_t* ks, const int64_t* k_off, int64_t packed_len,
+                                const void* wire, int64_t wire_stride_bytes, int32_t nranks,
+                                int32_t* idx_out, void* stream);
+
+/*
+ * Decode nranks idx16 payloads and their values (`vals`: nranks consecutive payloads of packed_len
+ * values of val_dtype, ARCTOPK_F32 or ARCTOPK_BF16) into the fp32 bucket, every element written.
+ * Per element
+ *   s = 0.0f + v_0 + v_1 + ...    the ranks' values at that element (bf16: f(v)), in rank order, fp32
+ *   m = s / world_size            correctly rounded (x 1/ws for a power of two, else a division)
+ *   gE == NULL : out = m;   gE != NULL : gE := fma(decay, m, gE);  out = gE
+ * -- for fp32 values the bits of arctopk_sparse_decode (accumulate 1, ARCTOPK_F32), for bf16 values
+ * those of arctopk_sparse_decode_wire16.  The work split is the merged route's there (a block
+ * composes a 4096-element chunk of a tensor in LDS from all ranks and writes it once); a chunk lies
+ * inside one 65,536-element block, so per rank the block reads that block's two table entries
+ * (clamped to [0, ks], ordered) and searches only that slice of lo16 for the chunk's two 16-bit
+ * bounds.  A reconstructed index outside the chunk or the tensor is skipped.
+ * ARCTOPK_EINVAL also as arctopk_sparse_idx16_unpack, for world_size < 1, another val_dtype, or
+ * offsets[0] != 0 (the chunks then do not cover the bucket: unpack, and decode as before).
+ */
+int arctopk_sparse_decode_idx16(void* out, int64_t numel, int32_t ntensors, const int64_t* offsets,
+                                const int64_t* ks, const int64_t* k_off, int64_t packed_len,
+                                const void* wire, int64_t wire_stride_bytes, const void* vals,
+                                int32_t val_dtype, int32_t nranks, int32_t world_size, void* gE,
+                                float decay, void* stream);
+
 /*
  * Momentum fold of a whole bucket, in place, stream-ordered, one launch per
  * ARCTOPK_SPARSE_MAX_BATCH tensors: for every tensor i,
