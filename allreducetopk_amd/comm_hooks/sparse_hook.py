@@ -173,7 +173,6 @@ class SparseState(HookState):
         self._workspace = None
         self._ws_bytes: Dict[tuple, int] = {}
         self._seg_geom: Dict[tuple, "_SegGeometry"] = {}  # row / column: per bucket layout and ratio
-        self._fold_in = None  # RandK "hash" under EF14: the select applies E (1) or the first-call copy (2)
         # Residual dtype (not in the reference): None keeps E (and EF21's gE) in
         # the bucket's dtype; torch.float32 keeps them in fp32 under a bf16 bucket (4 B, under EF21
         # 8 B, per element of a 2-B bucket, plus EF21's fp32 scratch of the largest bucket), so unsent
@@ -405,7 +404,7 @@ def _sparse_hook_impl(state: SparseState, bucket, c4: bool = False) -> "torch.fu
 
     if ef == N.EF21 and b not in state.error_dict:
         return _ef21_dense_first_call(state, bucket, group, world_size, mixed)
-    state._fold_in = None  # EF14's err_in where the select folds E itself
+    fold_in = None  # EF14's err_in where the select folds E := G + E itself
     if mixed:
         _mixed_fold(state, bucket, ef, stream)
     elif ef == N.EF14:
@@ -419,7 +418,7 @@ def _sparse_hook_impl(state: SparseState, bucket, c4: bool = False) -> "torch.fu
         # its write pass (arctopk_randk_select_ef14: its keys never read the data)
         # (and fp32 TopK folds it in its first pass: arctopk_topk_select_ef14)
         if _select_folds(state, dtype) and state.sparse_type == "tensor":
-            state._fold_in = int(err_in)
+            fold_in = int(err_in)
         else:
             N.check(L.arctopk_ef14_fold(input_tensor.data_ptr(), err.data_ptr(), total, int(err_in),
                                         dt, stream), "arctopk_ef14_fold")
@@ -431,7 +430,7 @@ def _sparse_hook_impl(state: SparseState, bucket, c4: bool = False) -> "torch.fu
 
     _compress_exchange(state, bucket, group, world_size, ef, state._call_ratio(), _reseed(state),
                        e_decay=decay, g_decay=decay, count_bits=True, ef14_folded=ef == N.EF14, wire16=wire16,
-                       mixed=mixed, idx16=idx16)
+                       mixed=mixed, idx16=idx16, fold_in=fold_in)
     state.idx16_calls += int(idx16)
     state.wire16_calls += int(wire16)
     state.mixed_calls += int(mixed)
@@ -580,29 +579,63 @@ def _exchange(state: SparseState, group, world_size: int, values, indices, value
     return values, indices, world_size, 3 if by_column else 1
 
 
+def _idx16_pack(L, lay, indices, numels, stream):
+    """TopK's int32 selection as it travels under ``index_wire="idx16"``, for _exchange: (the byte
+    buffer arctopk_sparse_idx16_pack fills, the layout's number of 65,536-element blocks)."""
+    wire_bytes = int(L.arctopk_sparse_idx16_bytes(*lay))
+    if wire_bytes < 0:
+        N.check(-wire_bytes, "arctopk_sparse_idx16_bytes")
+    wire = torch.empty(wire_bytes, dtype=torch.uint8, device=indices.device)
+    N.check(L.arctopk_sparse_idx16_pack(*lay, indices.data_ptr(), wire.data_ptr(), stream), "arctopk_sparse_idx16_pack")
+    return wire, sum((n + 65535) // 65536 for n in numels)
+
+
+def _decode(L, x, lay, sum_k, idx, vals, nranks, world_size, accumulate, gerr, g_decay, dt, stream, *, wire16,
+            scratch, wire_bytes) -> None:
+    """What _exchange returned, into the bucket ``x``.  ``wire_bytes`` not None: ``idx`` holds idx16 payloads
+    of that size; an fp32 bucket decodes them in one pass, anything else expands them to int32 first.  Then
+    ``wire16``; ``scratch`` not None (``mixed`` under EF21: the fold's scratch takes the fp32 sums); or ``dt``."""
+    if wire_bytes is not None:
+        if dt == N.F32:
+            rc = L.arctopk_sparse_decode_idx16(x, *lay, sum_k, idx.data_ptr(), wire_bytes, vals.data_ptr(),
+                                               N.BF16 if wire16 else N.F32, nranks, world_size, gerr, g_decay, stream)
+            if rc != N.EINVAL:  # (a layout that does not start at 0: as a bf16 bucket)
+                N.check(rc, "arctopk_sparse_decode_idx16")
+                return
+        wire, idx = idx, torch.empty(nranks * sum_k, dtype=torch.int32, device=idx.device)
+        N.check(L.arctopk_sparse_idx16_unpack(*lay, sum_k, wire.data_ptr(), wire_bytes, nranks, idx.data_ptr(), stream),
+                "arctopk_sparse_idx16_unpack")
+    if wire16:
+        N.check(L.arctopk_sparse_decode_wire16(x, *lay, sum_k, idx.data_ptr(), vals.data_ptr(), nranks, world_size,
+                                               accumulate, gerr, g_decay, stream), "arctopk_sparse_decode_wire16")
+    elif scratch is not None:
+        N.check(L.arctopk_sparse_decode_mixed21(x, gerr, scratch, *lay, sum_k, idx.data_ptr(), vals.data_ptr(), nranks,
+                                                world_size, g_decay, stream), "arctopk_sparse_decode_mixed21")
+    else:
+        N.check(L.arctopk_sparse_decode(x, *lay, sum_k, idx.data_ptr(), vals.data_ptr(), nranks, world_size,
+                                        accumulate, gerr, g_decay, dt, stream), "arctopk_sparse_decode")
+
+
 def _compress_exchange(state: SparseState, bucket, group, world_size: int, ef: int, ratio: float,
                        seed, e_decay: float, g_decay: float, count_bits: bool, on_values=None,
                        ef14_folded: bool = False, wire16: bool = False, mixed: bool = False,
-                       idx16: bool = False) -> None:
+                       idx16: bool = False, fold_in=None) -> None:
     """The compressed call after the EF pre-apply, on the caller's stream: select (TopK) or draw
     (RandK) the indices, gather the values, persist the residual (EF14: E[idx] = 0; EF21:
     E[idx] += e_decay * values), exchange (RandK: all-reduce; TopK: all-gather of values and
     indices) and decode into the bucket (EF21: gE += g_decay * out, out = gE).
     ``sparse_type`` "row" / "column": the per-segment select (arctopk_seg_select) with the tensors'
     totals as ``ks``; under EF14 the caller has folded E := G + E already and says so with
-    ``ef14_folded`` (the tensor path's fused folds go by ``state._fold_in`` as before).
+    ``ef14_folded``.  ``fold_in`` (0 or 1): EF14's err_in where the tensor path's select folds it.
     ``wire16`` (an fp32 bucket under ``wire_dtype=torch.bfloat16``): after the unchanged select,
     arctopk_sparse_pack_wire16 rounds the values to bf16 and writes the residual in place of
-    arctopk_sparse_residual; the values travel and count as 16 bits; arctopk_sparse_decode_wire16
-    decodes.
+    arctopk_sparse_residual; the values travel and count as 16 bits.
     ``mixed`` (a bf16 bucket under ``error_dtype=torch.float32``, after _mixed_fold): the selects
     read fp32 from E (EF14) or the scratch (EF21) and leave E alone; their own fp32 gather goes
     unused, and the reference draws and "hash" run none: arctopk_sparse_pack_mixed rounds the bf16
-    values from the source and writes the residual; EF21 decodes with arctopk_sparse_decode_mixed21.
+    values from the source and writes the residual.
     ``idx16`` (TopK under ``index_wire="idx16"``, not the column layout): behind all of the above
-    arctopk_sparse_idx16_pack turns the int32 selection into the byte buffer that travels in its
-    place; an fp32 bucket decodes it with arctopk_sparse_decode_idx16 (fp32 or bf16 values), anything
-    else expands it with arctopk_sparse_idx16_unpack and decodes as before.
+    _idx16_pack turns the int32 selection into the byte buffer that travels in its place.  Decode: _decode.
     Reference: sparse_hook.py:237-297 (and :363-410 for the large-batch hook)."""
     L = N.lib()
     input_tensor = bucket.buffer()
@@ -627,14 +660,14 @@ def _compress_exchange(state: SparseState, bucket, group, world_size: int, ef: i
     indices = torch.empty(sum_k, dtype=torch.int32, device=device)
     x = input_tensor.data_ptr()
     err = state.error_dict[b].data_ptr() if ef != N.EF_NONE else None
-    # what a select reads, as which dtype, where it gathers to, whether it zeroes EF14's E[idx]
-    # (:104) in its last pass, and EF14's err_in where it also folds E := G + E (:205) itself
+    # what a select reads, as which dtype, where it gathers to and whether it zeroes EF14's E[idx]
+    # (:104) in its last pass
     if mixed:
         src = err if fold14 else state._mixed_scratch.data_ptr()
-        sel_vals, sel_dt, zero, fold_in = None, N.F32, 0, None  # (sel_vals: allocated where a select gathers)
+        sel_vals, sel_dt, zero = None, N.F32, 0  # (sel_vals: allocated where a select gathers)
     else:
         src = err if fold14 else x
-        sel_vals, sel_dt, zero, fold_in = values, dt, int(fold14), state._fold_in if fold14 else None
+        sel_vals, sel_dt, zero = values, dt, int(fold14)
     if drawn:
         _reference_draws(state, indices, seg, numels, ks, k_off)
         if not mixed:
@@ -695,43 +728,14 @@ def _compress_exchange(state: SparseState, bucket, group, world_size: int, ef: i
         N.check(L.arctopk_sparse_residual(err, nt, a_off, a_k, a_ko, indices.data_ptr(), values.data_ptr(), ef,
                                           e_decay, dt, stream), "arctopk_sparse_residual")
 
-    by_column = seg is not None and seg.by_column
-    packed = None
-    if idx16:  # the indices as they travel
-        wire_bytes = int(L.arctopk_sparse_idx16_bytes(total, nt, a_off, a_k, a_ko))
-        if wire_bytes < 0:
-            N.check(-wire_bytes, "arctopk_sparse_idx16_bytes")
-        wire = torch.empty(wire_bytes, dtype=torch.uint8, device=device)
-        N.check(L.arctopk_sparse_idx16_pack(total, nt, a_off, a_k, a_ko, indices.data_ptr(), wire.data_ptr(), stream),
-                "arctopk_sparse_idx16_pack")
-        packed = (wire, sum((n + 65535) // 65536 for n in numels))
+    lay = (total, nt, a_off, a_k, a_ko)
+    packed = _idx16_pack(L, lay, indices, numels, stream) if idx16 else None  # the indices as they travel
     vals, idx, nranks, accumulate = _exchange(state, group, world_size, values, indices, value_bits, count_bits,
-                                              hashed=hashed, by_column=by_column, idx16=packed)
-    gerr = state.global_error_dict[b].data_ptr() if ef == N.EF21 else None
-    if idx16:
-        if dtype == torch.float32:  # one pass from the format into the bucket
-            rc = L.arctopk_sparse_decode_idx16(x, total, nt, a_off, a_k, a_ko, sum_k, idx.data_ptr(), wire_bytes,
-                                               vals.data_ptr(), N.BF16 if wire16 else N.F32, nranks, world_size,
-                                               gerr, g_decay, stream)
-            if rc != N.EINVAL:  # (a layout that does not start at 0: as a bf16 bucket)
-                N.check(rc, "arctopk_sparse_decode_idx16")
-                return
-        unpacked = torch.empty(nranks * sum_k, dtype=torch.int32, device=device)
-        N.check(L.arctopk_sparse_idx16_unpack(total, nt, a_off, a_k, a_ko, sum_k, idx.data_ptr(), wire_bytes, nranks,
-                                              unpacked.data_ptr(), stream), "arctopk_sparse_idx16_unpack")
-        idx = unpacked
-    if wire16:
-        N.check(L.arctopk_sparse_decode_wire16(x, total, nt, a_off, a_k, a_ko, sum_k, idx.data_ptr(), vals.data_ptr(),
-                                               nranks, world_size, accumulate, gerr, g_decay, stream),
-                "arctopk_sparse_decode_wire16")
-    elif mixed and ef == N.EF21:  # the fold's scratch is free again: it takes the fp32 sums
-        N.check(L.arctopk_sparse_decode_mixed21(x, gerr, src, total, nt, a_off, a_k, a_ko, sum_k, idx.data_ptr(),
-                                                vals.data_ptr(), nranks, world_size, g_decay, stream),
-                "arctopk_sparse_decode_mixed21")
-    else:
-        N.check(L.arctopk_sparse_decode(x, total, nt, a_off, a_k, a_ko, sum_k, idx.data_ptr(), vals.data_ptr(),
-                                        nranks, world_size, accumulate, gerr, g_decay, dt, stream),
-                "arctopk_sparse_decode")
+                                              hashed=hashed, by_column=seg is not None and seg.by_column,
+                                              idx16=packed)
+    _decode(L, x, lay, sum_k, idx, vals, nranks, world_size, accumulate,
+            state.global_error_dict[b].data_ptr() if ef == N.EF21 else None, g_decay, dt, stream, wire16=wire16,
+            scratch=src if mixed and ef == N.EF21 else None, wire_bytes=packed[0].numel() if idx16 else None)
 
 
 def _large_batch_ef21(state: SparseState, bucket, c4: bool) -> "torch.futures.Future[torch.Tensor]":

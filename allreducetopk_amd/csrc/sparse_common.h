@@ -11,14 +11,14 @@
 
 namespace arctopk {
 
-// first position in a[lo, hi) with a[p] >= target (a ascending), one wave
-__device__ __forceinline__ int64_t wave_lower_bound(const int32_t* __restrict__ a, int64_t lo, int64_t hi,
-                                                    int32_t target) {
+// first position in a[lo, hi) with a[p] >= target (a ascending: int32 indices, or their 16-bit halves), one wave
+template <typename T>
+__device__ __forceinline__ int64_t wave_lower_bound(const T* __restrict__ a, int64_t lo, int64_t hi, int32_t target) {
     const int lane = threadIdx.x & 63;
     while (hi - lo > 64) {
         const int64_t step = (hi - lo + 63) / 64;
         const int64_t p = lo + (int64_t)lane * step;
-        const bool pred = p < hi && a[p] < target;
+        const bool pred = p < hi && (int32_t)a[p] < target;
         const int c = __popcll(__ballot(pred));
         if (c == 0) return lo;
         const int64_t nlo = lo + (int64_t)(c - 1) * step + 1;
@@ -27,7 +27,7 @@ __device__ __forceinline__ int64_t wave_lower_bound(const int32_t* __restrict__ 
         lo = nlo;
     }
     const int64_t p = lo + lane;
-    return lo + __popcll(__ballot(p < hi && a[p] < target));
+    return lo + __popcll(__ballot(p < hi && (int32_t)a[p] < target));
 }
 
 }  // namespace arctopk
@@ -35,6 +35,8 @@ __device__ __forceinline__ int64_t wave_lower_bound(const int32_t* __restrict__ 
 // ---- the layout of a bucket's payload, batch by batch (sparse_mixed.hip, sparse_idx16.hip) ------
 // Each file has its own copy (the kernels take MixedBatch by value under the file's own name).
 namespace {
+
+typedef int32_t vi4_t __attribute__((ext_vector_type(4)));  // 16 B of indices
 
 struct MixedBatch {
     int64_t off[ARCTOPK_SPARSE_MAX_BATCH];

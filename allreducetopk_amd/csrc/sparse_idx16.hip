@@ -28,6 +28,7 @@
 
 #include "common.h"
 #include "mixed_common.h"
+#include "sparse_chunk.h"
 #include "sparse_common.h"
 
 namespace {
@@ -38,14 +39,11 @@ using arctopk::MeanScale;
 using arctopk::st_f4_nt;
 using arctopk::u4_t;
 using arctopk::vf4_t;
+using arctopk::wave_lower_bound;
 
 constexpr int kB = ARCTOPK_SPARSE_MAX_BATCH;
-constexpr int kChunk = 4096;    // elements of a tensor a decode block composes in LDS
-constexpr int kUnits = 4;       // 16-B units per lane per step, loads before stores
 constexpr int kBlockBits = 16;  // a block of the format: 65,536 elements of a tensor
 static_assert((1 << kBlockBits) % kChunk == 0, "a chunk must lie inside one block");
-
-typedef int32_t vi4_t __attribute__((ext_vector_type(4)));
 
 // next to a MixedBatch: where each tensor's table entries start, and (first batch only) the padding
 // the pack zeroes: lo16 entries [pad_lo, pad_lo + n_pad_lo), table entries [pad_t, pad_t + n_pad_t)
@@ -138,25 +136,6 @@ __device__ __forceinline__ void block_slice(const int32_t* __restrict__ Tt, int3
     j1 = max(j0, j1);
 }
 
-// first position in a[lo, hi) with a[p] >= target (a ascending), one wave (wave_lower_bound on halves)
-__device__ __forceinline__ int64_t wave_lower_bound16(const uint16_t* __restrict__ a, int64_t lo, int64_t hi,
-                                                      int32_t target) {
-    const int lane = threadIdx.x & 63;
-    while (hi - lo > 64) {
-        const int64_t step = (hi - lo + 63) / 64;
-        const int64_t p = lo + (int64_t)lane * step;
-        const bool pred = p < hi && (int32_t)a[p] < target;
-        const int c = __popcll(__ballot(pred));
-        if (c == 0) return lo;
-        const int64_t nlo = lo + (int64_t)(c - 1) * step + 1;
-        const int64_t phi = lo + (int64_t)c * step;
-        hi = phi < hi ? phi : hi;
-        lo = nlo;
-    }
-    const int64_t p = lo + lane;
-    return lo + __popcll(__ballot(p < hi && (int32_t)a[p] < target));
-}
-
 // ---- unpack --------------------------------------------------------------------------------
 // block (blk, tensor, rank): idx_out[j] = blk << 16 | lo16[j] over the block's slice
 __global__ void __launch_bounds__(256) k_idx16_unpack(MixedBatch b, Idx16Batch x, const uint8_t* __restrict__ wire,
@@ -178,12 +157,7 @@ __global__ void __launch_bounds__(256) k_idx16_unpack(MixedBatch b, Idx16Batch x
 __device__ __forceinline__ float val_f(const float* p) { return *p; }
 __device__ __forceinline__ float val_f(const uint16_t* p) { return bf_bits_f(*p); }
 
-// the mean of the sums, and under GE the new gE
-template <bool GE>
-__device__ __forceinline__ float final1(float s, float ge, const MeanScale& sc, float decay) {
-    const float m = sc(s);
-    return GE ? __fmaf_rn(decay, m, ge) : m;
-}
+// (final1<GE>, the mean of the sums and under GE the new gE: sparse_chunk.h)
 
 // block (x, y) composes elements [4096 x, 4096 (x + 1)) of tensor y: the chunk starts as zeros in
 // LDS; for each rank in order, waves 0 and 1 read the two table entries of the chunk's 65,536-element
@@ -225,7 +199,7 @@ __global__ void __launch_bounds__(256) k_decode_idx16(MixedBatch b, Idx16Batch x
         if (wave < 2) {
             int64_t j0, j1;
             block_slice(reinterpret_cast<const int32_t*>(wr + table_off) + x.tb[t], blk, nb, b.k[t], j0, j1);
-            const int64_t lb = wave_lower_bound16(lt, j0, j1, wave == 0 ? base : base + len);
+            const int64_t lb = wave_lower_bound(lt, j0, j1, wave == 0 ? base : base + len);
             if ((threadIdx.x & 63) == 0) s_lb[r & 1][wave] = lb;
         }
         __syncthreads();

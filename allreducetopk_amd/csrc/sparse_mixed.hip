@@ -26,6 +26,7 @@
 
 #include "common.h"
 #include "mixed_common.h"
+#include "sparse_chunk.h"
 #include "sparse_common.h"
 
 namespace {
@@ -39,12 +40,8 @@ using arctopk::u4_t;
 using arctopk::vf4_t;
 using arctopk::wave_lower_bound;
 
-constexpr int kB = ARCTOPK_SPARSE_MAX_BATCH;
-constexpr int kChunk = 4096;       // elements of a tensor a merged-decode block composes in LDS
-constexpr int kUnits = 4;          // 16-B units per lane per step, loads before stores
 constexpr int kStreamGrid = 4096;  // blocks of a whole-bucket stream at most
 
-typedef int32_t vi4_t __attribute__((ext_vector_type(4)));
 typedef uint32_t vu2_t __attribute__((ext_vector_type(2)));
 
 // ---- fold (error_dtype) --------------------------------------------------------------------
@@ -184,12 +181,7 @@ __global__ void __launch_bounds__(256) k_pack16(MixedBatch b, const float* __res
 }
 
 // ---- decode --------------------------------------------------------------------------------
-// the mean of the sums, and under GE the new gE
-template <bool GE>
-__device__ __forceinline__ float final1(float s, float ge, const MeanScale& sc, float decay) {
-    const float m = sc(s);
-    return GE ? __fmaf_rn(decay, m, ge) : m;
-}
+// (final1<GE>, the mean of the sums and under GE the new gE: sparse_chunk.h)
 
 // wire_dtype, merged: block (x, y) composes elements [4096 x, 4096 (x + 1)) of tensor y: the chunk
 // starts as zeros in LDS; for each rank in order, waves 0 and 1 find the rank's slice of (ascending)

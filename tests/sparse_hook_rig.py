@@ -19,6 +19,7 @@ import types
 import torch
 import torch.distributed as dist
 
+import sparse_idx16_format as F16
 from allreducetopk_amd import _native as N
 from allreducetopk_amd.bucket import SyntheticBucket, bucket_numel
 from allreducetopk_amd.comm_hooks import sparse_hook as SH
@@ -58,6 +59,12 @@ ARGS = {
     "arctopk_sparse_pack_wire16": "values E numel ntensors offsets ks k_off idx vals16 ef decay stream",
     "arctopk_sparse_decode_wire16": "out numel ntensors offsets ks k_off packed_len idx vals16 nranks world_size "
                                     "accumulate gE decay stream",
+    "arctopk_sparse_idx16_bytes": "numel ntensors offsets ks k_off",
+    "arctopk_sparse_idx16_pack": "numel ntensors offsets ks k_off idx wire stream",
+    "arctopk_sparse_idx16_unpack": "numel ntensors offsets ks k_off packed_len wire wire_stride_bytes nranks idx_out "
+                                   "stream",
+    "arctopk_sparse_decode_idx16": "out numel ntensors offsets ks k_off packed_len wire wire_stride_bytes vals "
+                                   "val_dtype nranks world_size gE decay stream",
 }
 _DT = {torch.float32: "f32", torch.bfloat16: "bf16", torch.int32: "i32", torch.uint8: "u8"}
 
@@ -86,7 +93,7 @@ class Recorder:
                 return name
         for t in self.made:
             if t.data_ptr() == p:
-                kind = "indices" if t.dtype == torch.int32 else "values"
+                kind = {torch.int32: "indices", torch.uint8: "wire"}.get(t.dtype, "values")
                 return f"{kind}.{_DT[t.dtype]}[{t.numel()}]"
         return "unknown"
 
@@ -109,6 +116,9 @@ class Recorder:
                 else:  # an int64 array, or NULL
                     rec[key] = "NULL" if a is None else [int(v) for v in a]
             self.trace.append({"call": name, **rec})
+            if name == "arctopk_sparse_idx16_bytes":  # the format's size of this layout
+                ends = rec["offsets"][1:] + [rec["numel"]]
+                return F16.wire_bytes([e - o for o, e in zip(rec["offsets"], ends)], rec["ks"])
             return WS_BYTES if name.endswith("_workspace_bytes") else 0
 
         return fn
@@ -132,6 +142,7 @@ def snapshot(st) -> dict:
     """What a hook call leaves in the state."""
     return {"comm_bits_this_round": int(st.comm_bits_this_round), "iter": int(st.iter),
             "mixed_calls": int(st.mixed_calls), "wire16_calls": int(st.wire16_calls),
+            "idx16_calls": int(st.idx16_calls),
             "last_k": [int(k) for k in getattr(st, "last_k", [])],
             "error_dtype": {int(b): _DT[t.dtype] for b, t in st.error_dict.items()},
             "global_error_dtype": {int(b): _DT[t.dtype] for b, t in st.global_error_dict.items()},
@@ -171,7 +182,7 @@ def patched(rec: Recorder):
             setattr(obj, name, val)
 
 
-def make_state(kind, source, ef, sparse_type, variant, ws, c4=False, **kw):
+def make_state(kind, source, ef, sparse_type, variant, ws, c4=False, index_wire=None, **kw):
     cls = SH4.SparseState if c4 else SH.SparseState
     group = types.SimpleNamespace(size=lambda: ws)
     st = cls(group, compress_ratio=RATIO, start_compress_iter=kw.pop("start_compress_iter", 0),
@@ -180,10 +191,11 @@ def make_state(kind, source, ef, sparse_type, variant, ws, c4=False, **kw):
     st.error_decay = DECAY
     st.error_dtype = torch.float32 if variant == "bf16+error_dtype" else None
     st.wire_dtype = torch.bfloat16 if variant == "fp32+wire_dtype" else None
+    st.index_wire = index_wire
     return st
 
 
-def run_case(kind, source, ef, sparse_type, variant, ws, ncalls=2, c4=False, large_batch=False):
+def run_case(kind, source, ef, sparse_type, variant, ws, ncalls=2, c4=False, large_batch=False, index_wire=None):
     """The traces of ``ncalls`` hook calls of one fresh state on bucket 0: per call the list of
     native calls and collectives in order, ending in the state's snapshot (or the exception's name)."""
     rec = Recorder()
@@ -194,7 +206,7 @@ def run_case(kind, source, ef, sparse_type, variant, ws, ncalls=2, c4=False, lar
     out = []
     with patched(rec):
         torch.manual_seed(1234)
-        st = make_state(kind, source, ef, sparse_type, variant, ws, c4=c4,
+        st = make_state(kind, source, ef, sparse_type, variant, ws, c4=c4, index_wire=index_wire,
                         **({"start_compress_iter": 2} if large_batch else {}))
         if large_batch:
             st.large_batch_init = True
@@ -208,7 +220,7 @@ def run_case(kind, source, ef, sparse_type, variant, ws, ncalls=2, c4=False, lar
                 try:
                     fut = hook(st, rec.bucket)
                     assert fut.done() and fut.value() is G
-                except TypeError as e:  # the large-batch hook's iteration 0
+                except (TypeError, ValueError) as e:  # the large-batch hook's iteration 0; idx16's column layout
                     rec.trace.append({"raised": type(e).__name__})
                 out.append(rec.trace + [{"state": snapshot(st)}])
         finally:
@@ -226,6 +238,14 @@ def matrix():
     for variant in VARIANTS:
         yield f"c4-randk-hash-ef14-row-{variant}-ws2", dict(kind="randk", source="hash", ef="ef14", sparse_type="row",
                                                            variant=variant, ws=2, c4=True)
+    # index_wire="idx16": TopK's "tensor" and "row"; RandK ignores it, the column layout refuses it
+    for ef, sp, variant, ws in itertools.product(EFS, ("tensor", "row"), VARIANTS, (1, 2)):
+        yield f"topk-None-{ef}-{sp}-{variant}-ws{ws}-idx16", dict(kind="topk", source=None, ef=ef, sparse_type=sp,
+                                                                 variant=variant, ws=ws, index_wire="idx16")
+    yield "randk-hash-ef14-tensor-fp32-ws2-idx16", dict(kind="randk", source="hash", ef="ef14", sparse_type="tensor",
+                                                      variant="fp32", ws=2, index_wire="idx16")
+    yield "raises-topk-None-ef14-column-fp32-ws2-idx16", dict(kind="topk", source=None, ef="ef14", sparse_type="column",
+                                                            variant="fp32", ws=2, index_wire="idx16")
 
 
 if __name__ == "__main__":

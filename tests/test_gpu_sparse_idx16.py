@@ -172,6 +172,69 @@ def test_a_remote_payload_that_holds_anything(vdtype):
     assert torch.equal(out_d.cpu()[:3], idxs[0]) and _intact(obuf, out_d) and _intact(wbuf, wire_d)
 
 
+@functools.lru_cache(None)
+def _edge_payloads(nranks):
+    """Four tensors at which chunk (4096) and block (65,536) edges exist, k about a quarter of each;
+    every rank's ascending indices hold element 0, the last element and the elements either side of
+    each edge, the rest drawn per rank: (shapes, ks, per rank the indices, per rank bf16 values)."""
+    shapes, ks = [[5], [4095], [4097], [65537]], [2, 1024, 1024, 16384]
+    g = torch.Generator().manual_seed(23)
+    all_idx, all_vals = [], []
+    for q in range(nranks):
+        idxs = []
+        for (n,), k in zip(shapes, ks):
+            forced = torch.tensor([e for e in (0, 4095, 4096, 65535, 65536, n - 1) if e < n]).unique()
+            free = torch.ones(n, dtype=torch.bool)
+            free[forced] = False
+            rest = free.nonzero().flatten()
+            rest = rest[torch.randperm(rest.numel(), generator=g)[:k - forced.numel()]]
+            idxs.append(torch.cat([forced, rest]).sort().values.to(torch.int32))
+        v = torch.randn(sum(ks), generator=g) * 2.0 ** (8 - 8 * q)
+        v[::9] = -0.0
+        all_idx.append(idxs)
+        all_vals.append(v.to(BF16))
+    return shapes, ks, all_idx, all_vals
+
+
+@pytest.mark.parametrize("nr", [1, 3])
+@pytest.mark.parametrize("ge", ["none", "aligned", "shifted"])
+@pytest.mark.parametrize("shift", [0, 1])
+def test_the_two_chunk_decodes_agree(shift, ge, nr):
+    """arctopk_sparse_decode_idx16 (bf16 values) and arctopk_sparse_decode_wire16 (accumulate 1) are the
+    same chunk decode over two index formats: on the same selection `out` and `gE` agree bit for
+    bit, with the bucket 16-B aligned or one element off and gE absent, aligned with `out`, or one
+    element off it (every element then goes the scalar way)."""
+    shapes, ks, all_idx, all_vals = _edge_payloads(nr)
+    numels, lay = _args(shapes, ks)
+    n, sum_k, stream = sum(numels), sum(ks), _stream()
+    wires = [torch.from_numpy(F.encode(numels, ks, torch.cat(ix).numpy()).copy()) for ix in all_idx]
+    wbuf, wire_d = _guarded(torch.cat(wires))
+    ibuf, idx_d = _guarded(torch.cat([torch.cat(ix) for ix in all_idx]))
+    vbuf, vals_d = _guarded(torch.cat(all_vals))
+    gE0 = _grad(n, 9, 0.37)
+    gE0[::5] = -0.0
+    got = []
+    for fmt in ("idx16", "int32"):
+        obuf, out_d = _guarded(torch.full((n,), 5.0), shift)
+        gbuf, gE_d = (None, None) if ge == "none" else _guarded(gE0, shift + (ge == "shifted"))
+        if fmt == "idx16":
+            rc = N.lib().arctopk_sparse_decode_idx16(out_d.data_ptr(), *lay, sum_k, wire_d.data_ptr(), wires[0].numel(),
+                                                     vals_d.data_ptr(), N.BF16, nr, nr, N.ptr(gE_d), 0.7, stream)
+        else:
+            rc = N.lib().arctopk_sparse_decode_wire16(out_d.data_ptr(), *lay, sum_k, idx_d.data_ptr(), vals_d.data_ptr(),
+                                                      nr, nr, 1, N.ptr(gE_d), 0.7, stream)
+        N.check(rc, fmt)
+        torch.cuda.synchronize()
+        assert _intact(obuf, out_d) and (gE_d is None or _intact(gbuf, gE_d)), fmt
+        got.append((out_d.cpu(), None if gE_d is None else gE_d.cpu()))
+    assert _intact(wbuf, wire_d) and _intact(ibuf, idx_d) and _intact(vbuf, vals_d)
+    _same_bits(got[0][0], got[1][0], "out")
+    assert not torch.equal(got[0][0], torch.full((n,), 5.0))
+    if ge != "none":
+        _same_bits(got[0][1], got[1][1], "gE")
+        _same_bits(got[0][1], got[0][0], "gE against out")
+
+
 # ---- the hooks ---------------------------------------------------------------------------
 CONFIGS = {"fp32": (F32, {}), "fp32_wire16": (F32, dict(wire_dtype=BF16)), "bf16": (BF16, {}),
            "bf16_err32": (BF16, dict(error_dtype=F32))}

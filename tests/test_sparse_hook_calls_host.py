@@ -15,6 +15,7 @@ TOTAL = 5 + 16 * 64 + 3 * 7 + 8 * 4 * 3 * 3
 NUMELS = [5, 1024, 21, 288]
 OFFSETS = [0, 5, 1029, 1050]
 VIEWS = [(1, 5), (16, 64), (3, 7), (8, 36)]  # [rows, cols]: 1-D is one row, N-D is [shape[0], rest]
+BLOCKS = 4  # 65,536-element blocks of the four tensors (index_wire="idx16")
 
 
 def layout(sparse_type, ratio):
@@ -32,9 +33,10 @@ def layout(sparse_type, ratio):
     return ks, k_off, rows, cols, k_seg
 
 
-def expected(kind, source, ef, sparse_type, variant, ws, call, ratio=R.RATIO):
+def expected(kind, source, ef, sparse_type, variant, ws, call, ratio=R.RATIO, index_wire=None):
     """(calls and collectives in order, each a name and the fields that must match; bits the call
     adds; whether it is EF21's dense first call)."""
+    idx16 = index_wire == "idx16" and kind == "topk"  # RandK sends no index
     random, hashed = kind == "randk", source == "hash"
     refdraw = random and not hashed
     seg, by_col = sparse_type != "tensor", sparse_type == "column"
@@ -103,6 +105,12 @@ def expected(kind, source, ef, sparse_type, variant, ws, call, ratio=R.RATIO):
     elif ef == "ef21" or (ef == "ef14" and refdraw):  # EF14's E[idx] = 0 is the select's otherwise
         seq.append(("arctopk_sparse_residual", dict(E=E, idx=idx, vals=sel_vals, ef=efc, decay=R.DECAY, dtype=dt,
                                                     **lay)))
+    # ---- index wire: the format's bytes (lo16 and the table of the 4 tensors' 4 blocks, each padded to 16 B)
+    wire_bytes = -(-2 * sum_k // 16) * 16 + -(-4 * BLOCKS // 16) * 16
+    wire = f"wire.u8[{wire_bytes}]"
+    if idx16:
+        seq.append(("arctopk_sparse_idx16_bytes", dict(numel=TOTAL, **lay)))
+        seq.append(("arctopk_sparse_idx16_pack", dict(numel=TOTAL, idx=idx, wire=wire, **lay)))
     # ---- exchange
     wdt = wire_vals.split(".")[1].split("[")[0]
     dec_idx, dec_vals = idx, wire_vals
@@ -112,13 +120,26 @@ def expected(kind, source, ef, sparse_type, variant, ws, call, ratio=R.RATIO):
             seq.append(("all_reduce", dict(dtype=wdt, numel=sum_k, buf=wire_vals)))
         nranks, accumulate = 1, 2 if hashed and not by_col else 0
     else:
-        bits = (ws - 1) * ws * sum_k * (vbits + 32)
+        # (section 4i: 16 bits per index and 32 per block, the padding not counted)
+        bits = (ws - 1) * ws * (sum_k * vbits + (sum_k * 16 + BLOCKS * 32 if idx16 else sum_k * 32))
         if ws > 1:
             seq.append(("all_gather", dict(dtype=wdt, numel=sum_k, out_numel=ws * sum_k, buf=wire_vals)))
-            seq.append(("all_gather", dict(dtype="i32", numel=sum_k, out_numel=ws * sum_k, buf=idx)))
+            if idx16:
+                seq.append(("all_gather", dict(dtype="u8", numel=wire_bytes, out_numel=ws * wire_bytes, buf=wire)))
+                wire = f"wire.u8[{ws * wire_bytes}]"
+            else:
+                seq.append(("all_gather", dict(dtype="i32", numel=sum_k, out_numel=ws * sum_k, buf=idx)))
             dec_idx, dec_vals = f"indices.i32[{ws * sum_k}]", f"values.{wdt}[{ws * sum_k}]"
         nranks, accumulate = ws, 3 if by_col else 1
     # ---- decode
+    if idx16:
+        fmt = dict(numel=TOTAL, packed_len=sum_k, wire=wire, wire_stride_bytes=wire_bytes, nranks=ws, **lay)
+        if f32:  # one pass from the format into the bucket
+            seq.append(("arctopk_sparse_decode_idx16", dict(out="bucket", vals=dec_vals, world_size=ws,
+                                                            val_dtype=N.BF16 if wire16 else N.F32,
+                                                            gE=gE if ef == "ef21" else "NULL", decay=R.DECAY, **fmt)))
+            return seq, bits, False
+        seq.append(("arctopk_sparse_idx16_unpack", dict(idx_out=dec_idx, **fmt)))
     dec = dict(out="bucket", numel=TOTAL, packed_len=sum_k, idx=dec_idx, nranks=nranks, world_size=ws,
                decay=R.DECAY, **lay)
     if wire16:
@@ -146,13 +167,14 @@ def check_trace(trace, seq, where):
         assert "unknown" not in t.values(), f"{where}: {name} got a pointer that is no buffer of the call: {t}"
 
 
-def check_state(snap, prev, kind, ef, variant, bits, dense, ks, where, count_bits=True):
+def check_state(snap, prev, kind, ef, variant, bits, dense, ks, where, count_bits=True, index_wire=None):
     f32 = variant.startswith("fp32")
     mixed = variant == "bf16+error_dtype" and ef != "noef"
     assert snap["iter"] == prev["iter"] + 1, where
     assert snap["comm_bits_this_round"] == prev["comm_bits_this_round"] + (bits if count_bits else 0), where
     assert snap["mixed_calls"] == prev["mixed_calls"] + int(mixed and not dense), where
     assert snap["wire16_calls"] == prev["wire16_calls"] + int(variant == "fp32+wire_dtype" and not dense), where
+    assert snap["idx16_calls"] == prev["idx16_calls"] + int(index_wire == "idx16" and kind == "topk" and not dense), where
     if not dense:
         assert snap["last_k"] == ks, where
     res = "f32" if f32 or mixed else "bf16"
@@ -167,12 +189,12 @@ def check_state(snap, prev, kind, ef, variant, bits, dense, ks, where, count_bit
 
 def _fresh(case):
     st = R.make_state(case["kind"], case["source"], case["ef"], case["sparse_type"], case["variant"], case["ws"],
-                      c4=case.get("c4", False))
+                      c4=case.get("c4", False), index_wire=case.get("index_wire"))
     torch.manual_seed(1234)
     return R.snapshot(st)
 
 
-MATRIX = [(cid, kw) for cid, kw in R.matrix() if not cid.startswith(("large_batch", "c4"))]
+MATRIX = [(cid, kw) for cid, kw in R.matrix() if not cid.startswith(("large_batch", "c4", "raises"))]
 
 
 @pytest.mark.parametrize("cid,case", MATRIX, ids=[cid for cid, _ in MATRIX])
@@ -185,8 +207,17 @@ def test_matrix(cid, case):
         check_trace(trace, seq, where)
         snap = trace[-1]["state"]
         check_state(snap, prev, case["kind"], case["ef"], case["variant"], bits, dense,
-                    layout(case["sparse_type"], R.RATIO)[0], where)
+                    layout(case["sparse_type"], R.RATIO)[0], where, index_wire=case.get("index_wire"))
         prev = snap
+
+
+def test_idx16_refuses_the_column_layout():
+    """``index_wire="idx16"`` with ``sparse_type="column"``: ValueError before any native call,
+    collective or change of the state."""
+    (cid, case), = [(c, k) for c, k in R.matrix() if c.startswith("raises")]
+    fresh = _fresh(case)
+    for trace in R.run_case(**case):
+        assert trace == [{"raised": "ValueError"}, {"state": fresh}], cid
 
 
 def test_the_torch_and_host_draws_differ_only_in_where_they_are_made():
