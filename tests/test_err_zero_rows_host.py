@@ -4,71 +4,26 @@
 
 (What the library itself then does with ``err_in = 2`` -- its own record of the slot map, the pack
 or finalize and the stream -- is tests/test_gpu_err_zero_rows.py.)"""
-import types
-
 import pytest
-import torch
 
 from allreducetopk_amd import _native as N
-from allreducetopk_amd.bucket import SyntheticBucket, bucket_numel
 from allreducetopk_amd.comm_hooks import group_topk_hook_no_reshape as H
 from allreducetopk_amd.comm_hooks import group_topk_hook_no_reshape_c4 as H4
-
-SHAPES = [[8, 64], [16]]
-
-
-class _Lib:
-    """Stands in for libarctopk: records the err_in of every step, fails on request."""
-
-    def __init__(self):
-        self.err_in = []
-        self.fail = 0
-
-    def arctopk_exchange_step(self, handle, x, e, g, ef, err_in, *rest):
-        self.err_in.append(err_in)
-        return self.fail
-
-    def arctopk_exchange_finish(self, *a):
-        return 0
-
-
-class _Plan:
-    """What the hook touches of a BucketPlan on the native path."""
-
-    def __init__(self):
-        self.handle = object()
-        self.slotmap = torch.zeros(24, dtype=torch.int32)
-        self.bits_sum = 0
-        self.philox_advance = 0
-        self.comm_registered = None
+from arc_hook_rig import rig as base_rig  # noqa: F401
 
 
 @pytest.fixture()
-def rig(monkeypatch):
-    lib = _Lib()
-    monkeypatch.setattr(H, "_LIB", [lib])
-    monkeypatch.setattr(N, "lib", lambda: lib)
-    monkeypatch.setattr(H, "_reseed_global", lambda *a, **k: None)
-    monkeypatch.setattr(H, "_current_raw_stream", lambda dix: 0)
-    monkeypatch.setattr(H, "_claim_projections", lambda *a, **k: False)
-    monkeypatch.setattr(H, "_predraw_target", lambda *a, **k: (None, 0))
-    group = types.SimpleNamespace(size=lambda: 1)  # (the hook only asks a group for its size here)
-    plans = {}
-
-    def make(cls=H.GroupTopKState, ef="ef14", **kw):
-        st = cls(group, r=4, compress_ratio=0.2, start_compress_iter=0, use_error_feedback=ef, **kw)
-        st.select_streams = "off"
-        st.defer_decode = False
-        st.trail_bytes = 0
-        st._plan_for = lambda bucket, buf=None: plans.setdefault((bucket.index(), st._plan_ratio()), _Plan())
-        return st
+def rig(base_rig):  # noqa: F811
+    """``call``: one hook call on bucket b, waited for; the err_in its step got."""
+    step = base_rig.call
 
     def call(st, b=0, hook=H.group_topk_hook):
-        G = torch.ones(bucket_numel(SHAPES))
-        hook(st, SyntheticBucket(G, SHAPES, index=b)).wait()
-        return lib.err_in[-1]
+        fut, trace = step(st, b=b, hook=hook)
+        fut.wait()
+        return [t["err_in"] for t in trace if t.get("call") == "arctopk_exchange_step"][-1]
 
-    return types.SimpleNamespace(lib=lib, make=make, call=call, plans=plans)
+    base_rig.call = call
+    return base_rig
 
 
 def test_first_call_then_steady_state(rig):
@@ -90,7 +45,7 @@ def test_in_place_edit_turns_it_off_for_one_call(rig):
     st.error_dict[0] = st.error_dict[0].clone()  # another tensor
     assert rig.call(st) == N.ERR_IN_READ
     assert rig.call(st) == N.ERR_IN_ZERO_ROWS
-    rig.plans[(0, 0.2)].slotmap.add_(1)  # a torch op on the slot map
+    rig.plan(st).slotmap.add_(1)  # a torch op on the slot map
     assert rig.call(st) == N.ERR_IN_READ
     assert rig.call(st) == N.ERR_IN_ZERO_ROWS
 
@@ -152,9 +107,9 @@ def test_other_ef_modes_never_pass_it(rig):
 def test_failed_step_resets(rig):
     st = rig.make()
     rig.call(st), rig.call(st)
-    rig.lib.fail = N.EINVAL
+    rig.rec.status["arctopk_exchange_step"] = N.EINVAL
     with pytest.raises(Exception):
         rig.call(st)
-    rig.lib.fail = 0
+    rig.rec.status["arctopk_exchange_step"] = 0
     assert rig.call(st) == N.ERR_IN_READ
     assert rig.call(st) == N.ERR_IN_ZERO_ROWS

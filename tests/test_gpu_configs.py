@@ -27,11 +27,15 @@ Bar (north_star: indices bit-exact, decompressed gradients within 1e-6):
 
 TopK / RandK select exactly (no sketch), so their outputs are bit-exact end to end.
 """
+import os
+
 import pytest
 import torch
 
+import arc_hook_rig as R
 from allreducetopk_amd import _native as N
 from allreducetopk_amd.bucket import SyntheticBucket, bucket_numel
+from allreducetopk_amd.comm_hooks import group_topk_hook_no_reshape as H
 from allreducetopk_amd.comm_hooks import sparse_hook
 from allreducetopk_amd.comm_hooks.group_topk_hook_no_reshape import GroupTopKState, group_topk_hook
 from workloads import WORKLOADS, ddp_buckets, resnet18_cifar_shapes, resnet50_cifar_shapes
@@ -380,3 +384,65 @@ def test_resnet50_mix_randk():
         assert_bitwise(out, res["out"], f"it{it} out")
         assert_bitwise(st.error_dict[0], res["E_new"][0], f"it{it} E")
         E = res["E_new"][0]
+
+
+# ---- the CPU rig's stub against the real calls (tests/arc_hook_rig.py) ---------------------------
+RIG_NAMES = ("arctopk_exchange_step", "arctopk_exchange_trail", "arctopk_exchange_finish")
+
+
+def _call_summary(name, a):
+    """What both sides are compared in: the entry point and, of a step, err_in, defer, whether a ride, a
+    trail and a select stream are present, and the length of the finish list."""
+    if name != "arctopk_exchange_step":
+        return (name,)
+    return (name, int(a[5]), int(a[14]), bool(a[15]), bool(a[23]), bool(a[22]), int(a[19]))
+
+
+@pytest.mark.parametrize("opts", [{}, {"select_streams": "on"},
+                                  {"force_exchange": True, "exchange_groups": "all", "group_bytes": 1024}],
+                         ids=["defaults", "select-on", "force-groups-all"])
+def test_real_calls_match_the_rig(opts, monkeypatch):
+    """Two backwards of three [[8, 64], [16]] buckets (fp32, EF14, defer_decode): the real library is called
+    with the same sequence of step / trail / finish, and per step the same err_in, defer, ride, trail, select
+    stream and finish count, as the CPU rig records for the scenario -- the rig's stub has not drifted.
+    (group_bytes 1024: so that a bucket this small is cut at all, into its two tensors.)"""
+    for v in [v for v in os.environ if v.startswith(R.ENV)]:  # an exported option would reach this side only
+        monkeypatch.delenv(v)
+    real, got = N.lib(), []
+
+    class Proxy:
+        def __getattr__(self, name):
+            fn = getattr(real, name)
+            if name not in RIG_NAMES:
+                return fn
+
+            def call(*a):
+                got.append(_call_summary(name, a))
+                return fn(*a)
+            return call
+
+    monkeypatch.setattr(N, "lib", lambda: Proxy())
+    monkeypatch.setattr(H, "_LIB", [Proxy()])
+    st = GroupTopKState(None, r=4, compress_ratio=0.2, start_compress_iter=0, use_error_feedback="ef14", seed=R.SEED)
+    st.defer_decode = True
+    for k, v in opts.items():
+        setattr(st, k, v)
+    g = torch.Generator(device=DEV).manual_seed(5)
+    for _ in range(2):
+        futs = [group_topk_hook(st, SyntheticBucket(torch.randn(bucket_numel(R.SHAPES), device=DEV, generator=g),
+                                                    R.SHAPES, index=b, is_last=b == 2)) for b in range(3)]
+        for f in futs:
+            f.wait()
+    torch.cuda.synchronize()
+    monkeypatch.setattr(N, "lib", lambda: real)  # (the rig puts its own in place, and this one back)
+    rig_opts = {k: v for k, v in opts.items() if k != "force_exchange"}
+    steps = R.run_case(world="ws1force" if opts.get("force_exchange") else "ws1", buckets=[R.SHAPES] * 3, ngroups=2,
+                       **rig_opts)
+    names = R.ARGS["arctopk_exchange_step"].split()
+    want = []
+    for step in steps:
+        for t in step["trace"]:
+            if t.get("call") in RIG_NAMES:
+                a = [t.get(k) for k in names]
+                want.append(_call_summary(t["call"], [0 if v == "NULL" else v for v in a]))
+    assert got == want

@@ -4,111 +4,28 @@ leaves alone, checkpoints, and the arithmetic the option exists for (the bf16 gl
 that drops a mean of half an ulp on every call; the restatement's gE == E at world size 1).
 
 (The kernels and the hook on a GPU: tests/test_gpu_mixed_ef21.py.)"""
-import types
-
 import pytest
 import torch
 
 import mixed_ef21_oracle as M21
 from allreducetopk_amd import _native as N
-from allreducetopk_amd.bucket import SyntheticBucket, bucket_numel
+from allreducetopk_amd.bucket import bucket_numel
 from allreducetopk_amd.comm_hooks import group_topk_hook_no_reshape as H
 from allreducetopk_amd.comm_hooks import group_topk_hook_no_reshape_c4 as H4
+from arc_hook_rig import SHAPES, rig as base_rig  # noqa: F401
 
-SHAPES = [[8, 64], [16]]
 BF16 = torch.bfloat16
 FP32 = torch.float32
 BRANCH = ["encode_mixed21", "select", "pack_mixed21", "decode_mixed21"]
 
 
-class _Lib:
-    """Stands in for libarctopk: records the native calls of a hook call in order."""
-
-    def __init__(self):
-        self.calls = []
-
-    def arctopk_exchange_step(self, handle, x, e, g, ef, err_in, *rest):
-        self.calls.append("exchange_step")
-        return 0
-
-    def arctopk_exchange_finish(self, *a):
-        return 0
-
-    def arctopk_encode_mixed(self, *a):
-        self.calls.append("encode_mixed")
-        return 0
-
-    def arctopk_pack_mixed(self, *a):
-        self.calls.append("pack_mixed")
-        return 0
-
-    def arctopk_encode_mixed21(self, handle, g, e, v, sk, stream):
-        self.calls.append("encode_mixed21")
-        return 0
-
-    def arctopk_pack_mixed21(self, handle, g, e, rl, sm, pk, stream):
-        self.calls.append("pack_mixed21")
-        return 0
-
-    def arctopk_decode_mixed21(self, handle, pk, sm, ws, ge, out, stream):
-        self.calls.append("decode_mixed21")
-        return 0
-
-
-class _Plan:
-    """What the hook touches of a BucketPlan."""
-
-    def __init__(self, lib):
-        self.lib = lib
-        self.handle = object()
-        self.slotmap = torch.zeros(24, dtype=torch.int32)
-        self.rowlist = torch.zeros(24, dtype=torch.int32)
-        self.sketch = torch.zeros(64, dtype=BF16)
-        self.packed = torch.zeros(64, dtype=BF16)
-        self.V_ring = [torch.zeros(256, dtype=BF16)]
-        self.info = types.SimpleNamespace(sketch_len=48, packed_len=64, v_len=256)
-        self.bits_sum = 1000
-        self.philox_advance = 0
-        self.comm_registered = None
-
-    def select(self, ws, stream, *a):
-        self.lib.calls.append("select")
-
-    def decode(self, ws, ef, gerr, out, stream):
-        self.lib.calls.append("decode")
-
-
 @pytest.fixture()
-def rig(monkeypatch):
-    lib = _Lib()
-    monkeypatch.delenv("ARCTOPK_ERROR_DTYPE", raising=False)
-    monkeypatch.delenv("ARCTOPK_EF21_ERROR_DTYPE", raising=False)
-    monkeypatch.setattr(H, "_LIB", [lib])
-    monkeypatch.setattr(N, "lib", lambda: lib)
-    monkeypatch.setattr(H, "_reseed_global", lambda *a, **k: None)
-    monkeypatch.setattr(H, "_current_raw_stream", lambda dix: 0)
-    monkeypatch.setattr(H, "_claim_projections", lambda *a, **k: False)
-    monkeypatch.setattr(H, "_predraw_target", lambda *a, **k: (None, 0))
-    monkeypatch.setattr(H.dist, "all_reduce", lambda *a, **k: None)  # (EF21's first call, one rank)
-    group = types.SimpleNamespace(size=lambda: 1)
-    plans = {}
-
-    def make(cls=H.GroupTopKState, ef="ef21", **kw):
-        st = cls(group, r=4, compress_ratio=0.2, start_compress_iter=0, use_error_feedback=ef, **kw)
-        st.select_streams = "off"
-        st.defer_decode = False
-        st.trail_bytes = 0
-        st._plan_for = lambda bucket, buf=None: plans.setdefault((bucket.index(), st._plan_ratio()), _Plan(lib))
-        return st
-
-    def call(st, dtype=BF16, b=0, hook=H.group_topk_hook):
-        del lib.calls[:]
-        G = torch.ones(bucket_numel(SHAPES), dtype=dtype)
-        fut = hook(st, SyntheticBucket(G, SHAPES, index=b))
-        assert fut.done()
-        return list(lib.calls)
-
-    return types.SimpleNamespace(lib=lib, make=make, call=call, plans=plans)
+def rig(base_rig):  # noqa: F811
+    """``call``: the names of the calls (a collective of the exchange with its count and dtype)."""
+    out = base_rig.brief({"comm_allreduce": ("count", "dtype")}, dtype=BF16, ef="ef21")
+    named = out.call
+    out.call = lambda st, **kw: [c if c[0] == "comm_allreduce" else c[0] for c in named(st, **kw)]
+    return out
 
 
 def test_default_and_environment(rig, monkeypatch):
@@ -130,7 +47,7 @@ def test_other_values_raise(rig, bad, ef):
     st.ef21_error_dtype = bad
     with pytest.raises(ValueError, match="ef21_error_dtype"):
         rig.call(st)
-    assert not st.error_dict and not st.global_error_dict and not rig.lib.calls
+    assert not st.error_dict and not st.global_error_dict and not rig.rec.trace
 
 
 def test_option_unset_is_the_existing_path(rig):
@@ -188,7 +105,7 @@ def test_error_dtype_alone_still_refuses_ef21(rig):
     with pytest.raises(ValueError, match="ef14") as ei:
         rig.call(st)
     assert "ef21_error_dtype" in str(ei.value)
-    assert not st.error_dict and not st.global_error_dict and not rig.lib.calls
+    assert not st.error_dict and not st.global_error_dict and not rig.rec.trace
 
 
 def test_switching_mid_run_is_an_error_not_a_reinterpretation(rig):
@@ -313,51 +230,23 @@ def test_oracle_invariant_at_world_size_one(dense_1d):
 
 
 # ---- the branch's collectives, pending deferred steps and bits ---------------------------------
-class _Comm:
-    handle = 1
-
-    def __init__(self):
-        self.registered = []
-
-    def register(self, t):
-        self.registered.append(t)
-
-    def check(self, status, what):
-        assert status == 0
-
-    def raise_if_failed(self):
-        pass
-
-
-def _with_comms(rig, st, ws=1):
-    """Stub exchange communicators for `st`, a group of `ws` ranks, and an all-reduce entry point
-    that records itself."""
-    st._test_comms = (_Comm(), _Comm())
-    st._exchange_comms = lambda group, dev: st._test_comms
-    st.process_group = types.SimpleNamespace(size=lambda: ws)
-    rig.lib.arctopk_comm_allreduce = lambda comm, buf, count, dtype, stream: rig.lib.calls.append(
-        ("allreduce", count, dtype)) or 0
-    return st
-
-
 def _branch_with_collectives(plan):
-    return ["encode_mixed21", ("allreduce", plan.info.sketch_len, N.BF16), "select", "pack_mixed21",
-            ("allreduce", plan.info.packed_len, N.BF16), "decode_mixed21"]
+    return ["encode_mixed21", ("comm_allreduce", plan.info.sketch_len, N.BF16), "select", "pack_mixed21",
+            ("comm_allreduce", plan.info.packed_len, N.BF16), "decode_mixed21"]
 
 
 @pytest.mark.parametrize("ws,force", [(1, True), (2, False)])
 def test_native_call_sequence_with_collectives(rig, ws, force):
-    st = rig.make()
+    st = rig.make(ws=ws)
     st.ef21_error_dtype = FP32
     st.force_exchange = force
-    _with_comms(rig, st, ws)
     assert rig.call(st) == []  # the dense first call (torch's process group)
     for _ in range(3):
         calls = rig.call(st)
-        plan = rig.plans[(0, st._plan_ratio())]
+        plan = rig.plan(st)
         assert calls == _branch_with_collectives(plan)
     # the plan's buffers are registered once per plan, not once per call
-    sk, pk = st._test_comms
+    sk, pk = st._comms[2:]
     assert len(sk.registered) == 1 and sk.registered[0] is plan.sketch
     assert len(pk.registered) == 1 and pk.registered[0] is plan.packed
     assert plan.comm_registered is pk and st.mixed_calls == 3
@@ -366,33 +255,31 @@ def test_native_call_sequence_with_collectives(rig, ws, force):
 def test_no_collectives_without_communicators(rig):
     st = rig.make()
     st.ef21_error_dtype = FP32
-    _with_comms(rig, st, 1)  # world size 1, no force_exchange, no emulated wire
+    # world size 1, no force_exchange, no emulated wire
     assert rig.call(st) == [] and rig.call(st) == BRANCH
-    assert not st._test_comms[0].registered and not st._test_comms[1].registered
+    assert not st._comms[2].registered and not st._comms[3].registered
 
 
 def test_pending_deferred_steps_are_finished_first(rig):
     st = rig.make()
     st.ef21_error_dtype = FP32
     st.defer_decode = True
-    rig.lib.arctopk_exchange_finish = lambda *a: rig.lib.calls.append("exchange_finish") or 0
     assert rig.call(st) == []  # bucket 0's dense first call
     # default-path calls of another bucket (fp32: the option does not apply); the second defers its decode
-    G = torch.ones(bucket_numel(SHAPES), dtype=FP32)
-    assert H.group_topk_hook(st, SyntheticBucket(G, SHAPES, index=1, is_last=False)).done()
-    fut = H.group_topk_hook(st, SyntheticBucket(G, SHAPES, index=1, is_last=False))
+    assert rig.call(st, dtype=FP32, b=1, is_last=False) == []
+    rig.call(st, dtype=FP32, b=1, is_last=False, done=False)
+    fut = rig.fut
     assert not fut.done() and len(st._x_pend) == 1
     assert rig.call(st) == ["exchange_finish"] + BRANCH
     assert fut.done() and not st._x_pend
 
 
 def test_bits_at_world_size_two(rig):
-    st = rig.make()
+    st = rig.make(ws=2)
     st.ef21_error_dtype = FP32
-    _with_comms(rig, st, 2)
     rig.call(st)
     first = st.comm_bits_this_round
     assert first == bucket_numel(SHAPES) * 16  # the dense first call's
     rig.call(st)
-    plan = rig.plans[(0, st._plan_ratio())]
-    assert st.comm_bits_this_round - first == 2 * (2 - 1) * plan.bits_sum == 2000
+    plan = rig.plan(st)
+    assert st.comm_bits_this_round - first == 2 * (2 - 1) * plan.bits_sum == 2 * (8 * 4 + 16 + 64 + 3) * 16

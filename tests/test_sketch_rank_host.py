@@ -8,14 +8,14 @@
 * a GroupTopKState(r=3) builds its plans and counts its bits with r = 3.
 """
 import ctypes
-import types
 
 import pytest
 import torch
 
 from allreducetopk_amd import _native as N
-from allreducetopk_amd.bucket import SyntheticBucket, bucket_numel
+from allreducetopk_amd.bucket import bucket_numel
 from allreducetopk_amd.comm_hooks import group_topk_hook_no_reshape as H
+from arc_hook_rig import rig  # noqa: F401
 from oracle import arctopk as A
 from sketch_rank import (N_SPLIT_F32, ORDER_DEPENDENT, RANK_MIX, energy_band, max_cols, sequential_energy)
 
@@ -134,25 +134,18 @@ def test_encode_tiles_accessor_checks_its_arguments():
 SHAPES = [[8, 64], [16], [4, 2, 3, 3]]
 
 
-def test_state_builds_plans_and_counts_bits_with_its_rank(monkeypatch):
-    """GroupTopKState(r=3) on the host path (native calls stubbed, no trailing step): the plan it
-    builds gets r = 3, and the bits one call sends are the oracle's for r = 3 (and not for r = 4)."""
-    real, bits_of = N.lib(), H.BucketPlan.bits_of
+def test_state_builds_plans_and_counts_bits_with_its_rank(rig, monkeypatch):  # noqa: F811
+    """GroupTopKState(r=3) on the host path (native calls recorded by the rig, the state's own _plan_for):
+    the plan it builds gets r = 3, and the bits one call sends are the oracle's for r = 3 (and not for r = 4)."""
+    real, bits_of = rig.rec.real_lib(), H.BucketPlan.bits_of
     built = []
-
-    class Lib:
-        def arctopk_exchange_step(self, *a):
-            return 0
-
-        def arctopk_exchange_finish(self, *a):
-            return 0
 
     class Plan:
         """What the hook touches of a BucketPlan; geometry from arctopk_plan_describe."""
 
         def __init__(self, shapes, r, ratio, dtype, device, flags=0):
             built.append((shapes, r, ratio))
-            self.r, self.ratio, self.flags, self.handle = r, ratio, flags, object()
+            self.r, self.ratio, self.flags, self.handle = r, ratio, flags, 0x100000
             dims = [int(d) for s in shapes for d in s]
             nd = [len(s) for s in shapes]
             segs = (N.Segment * len(shapes))()
@@ -168,23 +161,15 @@ def test_state_builds_plans_and_counts_bits_with_its_rank(monkeypatch):
             self.V_ring = [torch.zeros(int(self.info.v_len), dtype=dtype)]
             self.bits_sum = bits_of(self.segments, r, dtype)
             self.philox_advance = 0
-            self.comm_registered = None
+            self.comm_registered = self.packed16 = self.v_drawn = self.v_stream = None
 
-    lib = Lib()
-    monkeypatch.setattr(H, "_LIB", [lib])
-    monkeypatch.setattr(N, "lib", lambda: lib)
     monkeypatch.setattr(H, "BucketPlan", Plan)
     monkeypatch.setattr(H, "_check_bucket_layout", lambda buf, grads: None)  # (wants a device tensor)
-    monkeypatch.setattr(H, "_reseed_global", lambda *a, **k: None)
-    monkeypatch.setattr(H, "_current_raw_stream", lambda dix: 0)
-    monkeypatch.setattr(H, "_claim_projections", lambda *a, **k: False)
-    monkeypatch.setattr(H, "_predraw_target", lambda *a, **k: (None, 0))
-    st = H.GroupTopKState(types.SimpleNamespace(size=lambda: 1), r=3, compress_ratio=0.2, start_compress_iter=0,
-                          use_error_feedback="ef14")
-    st.select_streams, st.defer_decode, st.trail_bytes = "off", False, 0
+    st = rig.make(r=3)
+    del st._plan_for  # the state's own: it builds the plans
     for _ in range(2):
-        fut = H.group_topk_hook(st, SyntheticBucket(torch.ones(bucket_numel(SHAPES)), SHAPES, index=0))
-        assert fut.done()
+        fut, trace = rig.call(st, shapes=SHAPES)
+        assert fut.done() and [t["call"] for t in trace] == ["arctopk_exchange_step"]
     assert st.r == 3 and len(built) == 1
     assert built[0] == ([tuple(s) for s in SHAPES], 3, 0.2)
     plan = st._plans[0][1]

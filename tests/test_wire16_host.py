@@ -5,20 +5,19 @@ bucket makes with it, the bit accounting, checkpoints, and the entry points' hos
 (The kernels and the hook on a GPU: tests/test_gpu_wire16.py.)"""
 import ctypes
 import os
-import types
 
 import pytest
 import torch
 
 import wire16_oracle as W
 from allreducetopk_amd import _native as N
-from allreducetopk_amd.bucket import SyntheticBucket, bucket_numel
+from allreducetopk_amd.bucket import bucket_numel
 from allreducetopk_amd.build import LIB, build
 from allreducetopk_amd.comm_hooks import group_topk_hook_no_reshape as H
 from allreducetopk_amd.comm_hooks import group_topk_hook_no_reshape_c4 as H4
+from arc_hook_rig import SHAPES, rig as base_rig  # noqa: F401
 from oracle import arctopk as A
 
-SHAPES = [[8, 64], [16]]
 MIX = [[12, 20], [9], [6, 4, 3, 3], [33]]  # SKETCH, 1-D, ND, 1-D (RAW, or DENSE under the c4 rules)
 BF16 = torch.bfloat16
 
@@ -82,110 +81,14 @@ def test_two_rank_sum_is_one_rounding():
 
 
 # ---- 2. the option ---------------------------------------------------------------------------
-class _Lib:
-    """Stands in for libarctopk: records the native calls of a hook call in order."""
-
-    def __init__(self):
-        self.calls = []
-
-    def arctopk_exchange_step(self, handle, x, e, g, ef, err_in, *rest):
-        self.calls.append(("exchange_step", err_in))
-        return 0
-
-    def arctopk_exchange_finish(self, *a):
-        return 0
-
-    def arctopk_pack_wire16(self, handle, g, e, ef, err_in, rl, sm, pk, stream):
-        self.calls.append(("pack_wire16", ef, err_in))
-        return 0
-
-    def arctopk_decode_wire16(self, handle, pk, sm, ws, ef, gerr, out, stream):
-        self.calls.append(("decode_wire16", ef, ws))
-        return 0
-
-    def arctopk_comm_allreduce(self, comm, buf, count, dtype, stream):
-        self.calls.append(("allreduce", count, dtype))
-        return 0
-
-
-class _Plan:
-    """What the hook touches of a BucketPlan."""
-
-    def __init__(self, lib, dtype, shapes=SHAPES, ratio=0.2):
-        self.lib = lib
-        self.handle = object()
-        segs = W.segments(shapes, ratio)
-        self.segments = [types.SimpleNamespace(kind=s.kind, n=s.n, m=s.m, k_rows=s.k_rows) for s in segs]
-        self.r = 4
-        self.slotmap = torch.zeros(24, dtype=torch.int32)
-        self.rowlist = torch.zeros(24, dtype=torch.int32)
-        self.sketch = torch.zeros(64, dtype=dtype)
-        self.packed = torch.zeros(80, dtype=dtype)
-        self.V_ring = [torch.zeros(256, dtype=dtype)]
-        self.info = types.SimpleNamespace(sketch_len=W.sketch_elems(segs, 4), packed_len=80, v_len=256,
-                                          values_len=sum(s.k for s in segs))
-        self.bits_sum = 1000
-        self.philox_advance = 0
-        self.comm_registered = None
-        self.packed16 = None
-        self.packed16_registered = None
-
-    def encode(self, grad, err, ef, err_in, V, stream):
-        self.lib.calls.append(("encode", ef, int(err_in)))
-
-    def select(self, ws, stream, *a):
-        self.lib.calls.append(("select", ws))
-
-
-class _Comm:
-    handle = 1
-
-    def __init__(self):
-        self.registered = []
-
-    def register(self, t):
-        self.registered.append(t)
-
-    def check(self, status, what):
-        assert status == 0
-
-    def raise_if_failed(self):
-        pass
+# what the tests below compare of each record (the rest of it: tests/test_arc_hook_calls_host.py)
+FIELDS = {"exchange_step": ("err_in",), "encode": ("ef", "err_in"), "select": ("world_size",), "pack_wire16": ("ef", "err_in"),
+          "decode_wire16": ("ef", "world_size"), "comm_allreduce": ("count", "dtype")}
 
 
 @pytest.fixture()
-def rig(monkeypatch):
-    lib = _Lib()
-    for v in ("ARCTOPK_WIRE_DTYPE", "ARCTOPK_ERROR_DTYPE", "ARCTOPK_EF21_ERROR_DTYPE"):
-        monkeypatch.delenv(v, raising=False)
-    monkeypatch.setattr(H, "_LIB", [lib])
-    monkeypatch.setattr(N, "lib", lambda: lib)
-    monkeypatch.setattr(H, "_reseed_global", lambda *a, **k: None)
-    monkeypatch.setattr(H, "_current_raw_stream", lambda dix: 0)
-    monkeypatch.setattr(H, "_claim_projections", lambda *a, **k: False)
-    monkeypatch.setattr(H, "_predraw_target", lambda *a, **k: (None, 0))
-    plans = {}
-
-    def make(cls=H.GroupTopKState, ef="ef14", ws=1, **kw):
-        group = types.SimpleNamespace(size=lambda: ws)
-        st = cls(group, r=4, compress_ratio=0.2, start_compress_iter=0, use_error_feedback=ef, **kw)
-        st.select_streams = "off"
-        st.defer_decode = False
-        st.trail_bytes = 0
-        st._plan_for = lambda bucket, buf=None: plans.setdefault(
-            (id(st), bucket.index(), buf.dtype, st._plan_ratio()), _Plan(lib, buf.dtype))
-        st._test_comms = (_Comm(), _Comm())
-        st._exchange_comms = lambda group, dev: st._test_comms
-        return st
-
-    def call(st, dtype=torch.float32, b=0, hook=H.group_topk_hook):
-        del lib.calls[:]
-        G = torch.ones(bucket_numel(SHAPES), dtype=dtype)
-        fut = hook(st, SyntheticBucket(G, SHAPES, index=b))
-        assert fut.done()
-        return list(lib.calls)
-
-    return types.SimpleNamespace(lib=lib, make=make, call=call, plans=plans)
+def rig(base_rig):  # noqa: F811
+    return base_rig.brief(FIELDS)
 
 
 def test_default_and_environment(rig, monkeypatch):
@@ -207,7 +110,7 @@ def test_other_values_raise_at_the_first_compressed_call(rig, bad):
     st.wire_dtype = bad
     with pytest.raises(ValueError, match="wire_dtype"):
         rig.call(st)
-    assert not st.error_dict and not rig.lib.calls
+    assert not st.error_dict and not rig.rec.trace
 
 
 @pytest.mark.parametrize("ef,code", [("noef", N.EF_NONE), ("ef14", N.EF14)])
@@ -216,7 +119,7 @@ def test_fp32_bucket_takes_the_branch(rig, ef, code):
     st.wire_dtype = torch.bfloat16
     assert rig.call(st) == [("encode", code, 0 if ef == "ef14" else 1), ("select", 1), ("pack_wire16", code, 0 if ef == "ef14" else 1),
                             ("decode_wire16", code, 1)]
-    plan = next(iter(rig.plans.values()))
+    plan = rig.plan(st)
     assert plan.packed16.dtype == BF16 and plan.packed16.numel() == 80 and not plan.packed16.any()
     p16 = plan.packed16
     # the residual is read from the second call on; zero rows (err_in = 2) are never claimed
@@ -247,7 +150,7 @@ def test_host_staged_is_refused(rig):
     st.host_staged = True
     with pytest.raises(ValueError, match="host_staged"):
         rig.call(st)
-    assert not st.error_dict and not rig.lib.calls
+    assert not st.error_dict and not rig.rec.trace
 
 
 def test_state_dict_records_the_option_and_loads_under_either_setting(rig, tmp_path):
@@ -280,9 +183,9 @@ def test_bit_accounting(rig, ws):
     sk, k = W.sketch_elems(segs, 4), sum(s.k for s in segs)
     assert st.comm_bits_this_round == 2 * (ws - 1) * (sk * 32 + k * 16) == 2 * (ws - 1) * W.bits_per_call(segs, 4)
     # the sketch goes out in fp32, the packed values in bf16, the latter over the registered bf16 buffer
-    assert [c for c in calls if c[0] == "allreduce"] == [("allreduce", sk, N.F32), ("allreduce", 80, N.BF16)]
-    plan = next(p for p in rig.plans.values() if p.packed16 is not None)
-    assert any(t is plan.packed16 for t in st._test_comms[1].registered)
+    assert [c for c in calls if c[0] == "comm_allreduce"] == [("comm_allreduce", sk, N.F32), ("comm_allreduce", 80, N.BF16)]
+    plan = rig.plan(st)
+    assert any(t is plan.packed16 for t in st._comms[3].registered)
     # half the default path's bits for the values
     assert W.bits_per_call(segs, 4) == A.bits_per_call(segs, 4, 32) - k * 16
 
@@ -310,10 +213,9 @@ def test_pending_deferred_steps_are_finished_first(rig):
     st = rig.make()
     st.wire_dtype = torch.bfloat16
     st.defer_decode = True
-    rig.lib.arctopk_exchange_finish = lambda *a: rig.lib.calls.append(("exchange_finish",)) or 0
     # a default-path call of another bucket (bf16: the option does not apply) that defers its decode
-    G = torch.ones(bucket_numel(SHAPES), dtype=BF16)
-    fut = H.group_topk_hook(st, SyntheticBucket(G, SHAPES, index=1, is_last=False))
+    rig.call(st, dtype=BF16, b=1, is_last=False, done=False)
+    fut = rig.fut
     assert not fut.done() and len(st._x_pend) == 1
     calls = rig.call(st)
     assert calls == [("exchange_finish",), ("encode", N.EF14, 0), ("select", 1), ("pack_wire16", N.EF14, 0),
@@ -325,7 +227,7 @@ def test_bits_at_world_size_two(rig):
     st = rig.make(ws=2)
     st.wire_dtype = torch.bfloat16
     rig.call(st)
-    plan = next(p for p in rig.plans.values() if p.packed16 is not None)
+    plan = rig.plan(st)
     sketch_elems = sum(s.n * plan.r if s.kind == N.SEG_SKETCH else s.n if s.kind == N.SEG_RAW else 0
                        for s in plan.segments)
     assert st.comm_bits_this_round == 2 * (2 - 1) * (sketch_elems * 32 + plan.info.values_len * 16)
