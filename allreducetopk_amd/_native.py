@@ -171,6 +171,16 @@ _SIGS = {
     "arctopk_sparse_decode_idx16": (c_int32, [c_void_p, c_int64, c_int32, POINTER(c_int64), POINTER(c_int64),
                                               POINTER(c_int64), c_int64, c_void_p, c_int64, c_void_p, c_int32,
                                               c_int32, c_int32, c_void_p, c_float, c_void_p]),
+    "arctopk_sparse_bitmap_bytes": (c_int64, [c_int64, c_int32, POINTER(c_int64), POINTER(c_int64),
+                                             POINTER(c_int64)]),
+    "arctopk_sparse_bitmap_pack": (c_int32, [c_int64, c_int32, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64),
+                                            c_void_p, c_void_p, c_void_p]),
+    "arctopk_sparse_bitmap_unpack": (c_int32, [c_int64, c_int32, POINTER(c_int64), POINTER(c_int64),
+                                              POINTER(c_int64), c_int64, c_void_p, c_int64, c_int32, c_void_p,
+                                              c_void_p]),
+    "arctopk_sparse_decode_bitmap": (c_int32, [c_void_p, c_int64, c_int32, POINTER(c_int64), POINTER(c_int64),
+                                              POINTER(c_int64), c_int64, c_void_p, c_int64, c_void_p, c_int32,
+                                              c_int32, c_int32, c_void_p, c_float, c_void_p]),
     "arctopk_ef_apply": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p]),
     "arctopk_draw_bf16_normal": (c_int32, [c_uint64, c_int64, c_void_p]),
     "arctopk_draw_normal": (c_int32, [c_uint64, c_int32, c_int32, POINTER(c_int64), c_void_p]),

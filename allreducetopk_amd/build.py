@@ -28,14 +28,14 @@ LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "libarctopk.so")
 SOURCES = ["plan.hip", "arctopk_kernels.hip", "sparse_kernels.hip", "seg_select.hip", "mselect.hip", "vdraw.hip",
            "projection.cpp", "step.cpp", "exchange.cpp", "wire.hip", "momentum.hip", "mixed_ef.hip", "wire16.hip",
-           "sparse_mixed.hip", "sparse_idx16.hip"]
+           "sparse_mixed.hip", "sparse_idx16.hip", "sparse_bitmap.hip"]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wall",
          "-Wno-unused-function"]
 # per-source flags on top of FLAGS: new files keep the compiler from choosing the packed fp32
 # instructions (v_pk_add_f32, v_pk_mul_f32, v_pk_fma_f32); the older files' machine code stays as it is
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-SOURCE_FLAGS = {"sparse_idx16.hip": NO_PACKED_FP32}
+SOURCE_FLAGS = {"sparse_idx16.hip": NO_PACKED_FP32, "sparse_bitmap.hip": NO_PACKED_FP32}
 HASH_RE = re.compile(rb"src:([0-9a-f]{16})")
 
 

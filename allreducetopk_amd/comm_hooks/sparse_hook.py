@@ -90,6 +90,24 @@ without ``wire_dtype`` and ``error_dtype``); behind them such a call runs
 also at world size 1.  ``sparse_type`` "tensor" and "row" only: "column" (whose indices do not
 ascend) and ``large_batch_init`` raise ValueError; RandK (no index on the wire), the dense warm-up
 calls and EF21's dense first call ignore the option.
+
+``SparseState.index_wire = "bitmap"`` (environment default
+``ARCTOPK_SPARSE_INDEX_WIRE=bitmap``) sends the same selection as one bit per element of every tensor
+plus one int32 per 4096-element chunk (the format: include/arctopk.h): n_i + 32 ceil(n_i / 4096) bits
+per tensor whatever k is, fewer than idx16's above a ratio of about 0.063.  It behaves as "idx16" in
+every respect but the format:
+
+    pack    arctopk_sparse_bitmap_pack  the int32 selection -> one byte buffer; all_gather(values),
+            all_gather(bytes)
+    decode  an fp32 bucket (fp32 or bf16 values): arctopk_sparse_decode_bitmap finds every value by
+            popcount and writes the bucket in one pass | a bf16 bucket: arctopk_sparse_bitmap_unpack,
+            then the decode above
+
+``index_wire = "auto"`` (``ARCTOPK_SPARSE_INDEX_WIRE=auto``) takes, per compressed call, whichever of
+the two formats has fewer payload bytes for that call's layout (arctopk_sparse_bitmap_bytes against
+arctopk_sparse_idx16_bytes; a tie goes to idx16).  Both depend on shapes and ks alone, so every rank
+chooses alike without talking; under the c4 ramp the choice starts as bitmap and may end as idx16.
+``bitmap_calls`` and ``idx16_calls`` count what travelled.
 """
 
 import logging
@@ -143,6 +161,9 @@ def cal_k_by_column(tensor, compress_ratio):
     return max(1, int(v[0] * compress_ratio)) * v[1]
 
 
+_INDEX_WIRES = ("idx16", "bitmap", "auto")  # SparseState.index_wire, beside None
+
+
 class SparseState(HookState):
     """State of the TopK/RandK hook (reference sparse_hook.py:127-160)."""
 
@@ -194,12 +215,15 @@ class SparseState(HookState):
         self.wire_dtype = torch.bfloat16 if env == "bf16" else None
         self.wire16_calls = 0  # compressed calls that sent bf16 values of an fp32 bucket
         # Index wire (not in the reference): None sends TopK's indices as int32;
-        # "idx16" as 16-bit block offsets and a table of block starts.  Ignored by RandK.
+        # "idx16" as 16-bit block offsets and a table of block starts; "bitmap" (section 4j) as one bit
+        # per element and a table of chunk starts; "auto" as whichever of the two is smaller for the
+        # call's layout.  Ignored by RandK.
         env = os.environ.get("ARCTOPK_SPARSE_INDEX_WIRE", "")
-        if env not in ("", "idx16"):
-            raise ValueError(f"ARCTOPK_SPARSE_INDEX_WIRE must be 'idx16' (or unset), got {env!r}")
-        self.index_wire = "idx16" if env == "idx16" else None
-        self.idx16_calls = 0  # compressed calls that sent their indices so
+        if env not in ("",) + _INDEX_WIRES:
+            raise ValueError(f"ARCTOPK_SPARSE_INDEX_WIRE must be 'idx16', 'bitmap' or 'auto' (or unset), got {env!r}")
+        self.index_wire = env or None
+        self.idx16_calls = 0  # compressed calls that sent their indices as idx16
+        self.bitmap_calls = 0  # ... and as a bitmap
 
     # ratio of this call; the c4 variant overrides (gradual compression)
     def _call_ratio(self) -> float:
@@ -225,19 +249,19 @@ class SparseState(HookState):
             raise ValueError(f"wire_dtype must be None or torch.bfloat16, got {wd!r}")
         return wd is not None and bucket_dtype == torch.float32
 
-    def _idx16(self) -> bool:
-        """Whether this call sends its indices as 16-bit block offsets.  ValueError for an
-        ``index_wire`` other than None / "idx16", and for the column layout, whose indices do not
-        ascend; ignored by RandK, which sends no index."""
+    def _idx16(self):
+        """The index format this call asks for: None (int32), "idx16", "bitmap" or "auto".  ValueError
+        for any other ``index_wire``, and for the column layout, whose indices do not ascend; ignored by
+        RandK, which sends no index."""
         iw = self.index_wire
-        if iw is not None and iw != "idx16":
-            raise ValueError(f"index_wire must be None or 'idx16', got {iw!r}")
+        if iw is not None and not (isinstance(iw, str) and iw in _INDEX_WIRES):
+            raise ValueError(f"index_wire must be None, 'idx16', 'bitmap' or 'auto', got {iw!r}")
         if iw is None or self.random:
-            return False
+            return None
         if self.sparse_type == "column":
-            raise ValueError("index_wire='idx16' does not run with sparse_type='column': the format needs "
+            raise ValueError(f"index_wire={iw!r} does not run with sparse_type='column': the format needs "
                              "every tensor's indices ascending")
-        return True
+        return iw
 
     def state_dict(self) -> dict:
         out = super().state_dict()
@@ -374,8 +398,8 @@ def _sparse_hook_impl(state: SparseState, bucket, c4: bool = False) -> "torch.fu
             raise ValueError("wire_dtype=torch.bfloat16 does not run with large_batch_init: that hook "
                              "keeps a float32 bucket's float32 wire")
         if state._idx16():
-            raise ValueError("index_wire='idx16' does not run with large_batch_init: that hook keeps the "
-                             "int32 index wire")
+            raise ValueError(f"index_wire={state.index_wire!r} does not run with large_batch_init: that hook "
+                             "keeps the int32 index wire")
         return _large_batch_ef21(state, bucket, c4)
     state.maybe_accumulate_momentum_on_bucket(bucket)
     group = state.process_group if state.process_group is not None else dist.group.WORLD
@@ -400,7 +424,7 @@ def _sparse_hook_impl(state: SparseState, bucket, c4: bool = False) -> "torch.fu
     decay = float(state.error_decay)
     wire16 = state._wire16(dtype)  # bf16 values of this fp32 bucket on the wire (wire_dtype)
     mixed = state._mixed_residual(dtype, ef)  # fp32 residuals under this bf16 bucket (error_dtype)
-    idx16 = state._idx16()  # TopK's indices as 16-bit block offsets on the wire (index_wire)
+    idx16 = state._idx16()  # TopK's index format on the wire (index_wire): None, "idx16", "bitmap", "auto"
 
     if ef == N.EF21 and b not in state.error_dict:
         return _ef21_dense_first_call(state, bucket, group, world_size, mixed)
@@ -428,10 +452,11 @@ def _sparse_hook_impl(state: SparseState, bucket, c4: bool = False) -> "torch.fu
         N.check(L.arctopk_ef_apply(input_tensor.data_ptr(), err.data_ptr(),
                                    total, N.EF21, 1, dt, stream), "arctopk_ef_apply")
 
-    _compress_exchange(state, bucket, group, world_size, ef, state._call_ratio(), _reseed(state),
-                       e_decay=decay, g_decay=decay, count_bits=True, ef14_folded=ef == N.EF14, wire16=wire16,
-                       mixed=mixed, idx16=idx16, fold_in=fold_in)
-    state.idx16_calls += int(idx16)
+    sent = _compress_exchange(state, bucket, group, world_size, ef, state._call_ratio(), _reseed(state),
+                              e_decay=decay, g_decay=decay, count_bits=True, ef14_folded=ef == N.EF14, wire16=wire16,
+                              mixed=mixed, idx16=idx16, fold_in=fold_in)
+    state.idx16_calls += int(sent == "idx16")
+    state.bitmap_calls += int(sent == "bitmap")
     state.wire16_calls += int(wire16)
     state.mixed_calls += int(mixed)
     return _done(state, bucket, input_tensor)
@@ -552,10 +577,11 @@ def _exchange(state: SparseState, group, world_size: int, values, indices, value
     indices.  Returns what the decode reads: (values, indices, nranks, accumulate code).
     RandK "hash" outside the column layout: every tensor's indices ascend, so the decode may compose
     whole chunks in one pass (accumulate 2).
-    ``idx16`` (TopK under ``index_wire="idx16"``): (this rank's packed index bytes, the layout's
-    number of 65,536-element blocks); the byte buffers are gathered in place of the indices and
-    returned in their place.  Counted are the format's information bits, 16 per index and 32 per
-    block; its padding to 16 B (at most 30 bytes per rank) is not."""
+    ``idx16`` (TopK under ``index_wire``): (this rank's packed index bytes, the format's number of int32
+    table entries[, the bits of its body: 16 per index unless given]); the byte buffers are gathered
+    in place of the indices and returned in their place.  Counted are the format's information bits
+    -- idx16: 16 per index and 32 per 65,536-element block; bitmap: one per element and 32 per
+    4096-element chunk; its padding to 16 B (at most 30 bytes per rank) is not."""
     sum_k = indices.numel()
     if state.random:
         if count_bits:
@@ -564,8 +590,8 @@ def _exchange(state: SparseState, group, world_size: int, values, indices, value
             dist.all_reduce(values, group=group, async_op=False)
         return values, indices, 1, 2 if hashed and not by_column else 0
     if idx16 is not None:
-        indices, blocks = idx16
-        index_bits = sum_k * 16 + blocks * 32
+        indices, entries, *body = idx16
+        index_bits = (body[0] if body else sum_k * 16) + entries * 32
     else:
         index_bits = sum_k * 32
     if count_bits:
@@ -579,32 +605,43 @@ def _exchange(state: SparseState, group, world_size: int, values, indices, value
     return values, indices, world_size, 3 if by_column else 1
 
 
-def _idx16_pack(L, lay, indices, numels, stream):
-    """TopK's int32 selection as it travels under ``index_wire="idx16"``, for _exchange: (the byte
-    buffer arctopk_sparse_idx16_pack fills, the layout's number of 65,536-element blocks)."""
-    wire_bytes = int(L.arctopk_sparse_idx16_bytes(*lay))
-    if wire_bytes < 0:
-        N.check(-wire_bytes, "arctopk_sparse_idx16_bytes")
-    wire = torch.empty(wire_bytes, dtype=torch.uint8, device=indices.device)
-    N.check(L.arctopk_sparse_idx16_pack(*lay, indices.data_ptr(), wire.data_ptr(), stream), "arctopk_sparse_idx16_pack")
-    return wire, sum((n + 65535) // 65536 for n in numels)
+def _index_pack(L, lay, indices, numels, fmt, stream):
+    """TopK's int32 selection as it travels under ``index_wire`` ``fmt``: (the format, "idx16" or
+    "bitmap" -- "auto": the one with fewer payload bytes for this layout, a tie to idx16 -- then
+    _exchange's tuple: the byte buffer arctopk_sparse_<format>_pack fills, the format's table
+    entries[, bitmap: its n bits of body])."""
+    sizes = {}
+    for f in ("idx16", "bitmap") if fmt == "auto" else (fmt,):
+        name = f"arctopk_sparse_{f}_bytes"
+        sizes[f] = int(getattr(L, name)(*lay))
+        if sizes[f] < 0:
+            N.check(-sizes[f], name)
+    fmt = min(sizes, key=sizes.get)  # (the first of equal sizes: idx16)
+    wire = torch.empty(sizes[fmt], dtype=torch.uint8, device=indices.device)
+    name = f"arctopk_sparse_{fmt}_pack"
+    N.check(getattr(L, name)(*lay, indices.data_ptr(), wire.data_ptr(), stream), name)
+    if fmt == "idx16":
+        return fmt, (wire, sum((n + 65535) // 65536 for n in numels))
+    return fmt, (wire, sum((n + 4095) // 4096 for n in numels), sum(numels))
 
 
 def _decode(L, x, lay, sum_k, idx, vals, nranks, world_size, accumulate, gerr, g_decay, dt, stream, *, wire16,
-            scratch, wire_bytes) -> None:
-    """What _exchange returned, into the bucket ``x``.  ``wire_bytes`` not None: ``idx`` holds idx16 payloads
-    of that size; an fp32 bucket decodes them in one pass, anything else expands them to int32 first.  Then
-    ``wire16``; ``scratch`` not None (``mixed`` under EF21: the fold's scratch takes the fp32 sums); or ``dt``."""
-    if wire_bytes is not None:
+            scratch, idx16=None, wire_bytes=None) -> None:
+    """What _exchange returned, into the bucket ``x``.  ``idx16`` not None (the format, "idx16" or "bitmap"):
+    ``idx`` holds payloads of that format, ``wire_bytes`` each; an fp32 bucket decodes them in one pass,
+    anything else expands them to int32 first.  Then ``wire16``; ``scratch`` not None (``mixed`` under
+    EF21: the fold's scratch takes the fp32 sums); or ``dt``."""
+    if idx16 is not None:
         if dt == N.F32:
-            rc = L.arctopk_sparse_decode_idx16(x, *lay, sum_k, idx.data_ptr(), wire_bytes, vals.data_ptr(),
-                                               N.BF16 if wire16 else N.F32, nranks, world_size, gerr, g_decay, stream)
+            name = f"arctopk_sparse_decode_{idx16}"
+            rc = getattr(L, name)(x, *lay, sum_k, idx.data_ptr(), wire_bytes, vals.data_ptr(),
+                                  N.BF16 if wire16 else N.F32, nranks, world_size, gerr, g_decay, stream)
             if rc != N.EINVAL:  # (a layout that does not start at 0: as a bf16 bucket)
-                N.check(rc, "arctopk_sparse_decode_idx16")
+                N.check(rc, name)
                 return
         wire, idx = idx, torch.empty(nranks * sum_k, dtype=torch.int32, device=idx.device)
-        N.check(L.arctopk_sparse_idx16_unpack(*lay, sum_k, wire.data_ptr(), wire_bytes, nranks, idx.data_ptr(), stream),
-                "arctopk_sparse_idx16_unpack")
+        name = f"arctopk_sparse_{idx16}_unpack"
+        N.check(getattr(L, name)(*lay, sum_k, wire.data_ptr(), wire_bytes, nranks, idx.data_ptr(), stream), name)
     if wire16:
         N.check(L.arctopk_sparse_decode_wire16(x, *lay, sum_k, idx.data_ptr(), vals.data_ptr(), nranks, world_size,
                                                accumulate, gerr, g_decay, stream), "arctopk_sparse_decode_wire16")
@@ -619,7 +656,7 @@ def _decode(L, x, lay, sum_k, idx, vals, nranks, world_size, accumulate, gerr, g
 def _compress_exchange(state: SparseState, bucket, group, world_size: int, ef: int, ratio: float,
                        seed, e_decay: float, g_decay: float, count_bits: bool, on_values=None,
                        ef14_folded: bool = False, wire16: bool = False, mixed: bool = False,
-                       idx16: bool = False, fold_in=None) -> None:
+                       idx16=None, fold_in=None):
     """The compressed call after the EF pre-apply, on the caller's stream: select (TopK) or draw
     (RandK) the indices, gather the values, persist the residual (EF14: E[idx] = 0; EF21:
     E[idx] += e_decay * values), exchange (RandK: all-reduce; TopK: all-gather of values and
@@ -634,8 +671,9 @@ def _compress_exchange(state: SparseState, bucket, group, world_size: int, ef: i
     read fp32 from E (EF14) or the scratch (EF21) and leave E alone; their own fp32 gather goes
     unused, and the reference draws and "hash" run none: arctopk_sparse_pack_mixed rounds the bf16
     values from the source and writes the residual.
-    ``idx16`` (TopK under ``index_wire="idx16"``, not the column layout): behind all of the above
-    _idx16_pack turns the int32 selection into the byte buffer that travels in its place.  Decode: _decode.
+    ``idx16`` (TopK's index format under ``index_wire``: "idx16", "bitmap" or "auto"; not the column
+    layout): behind all of the above _index_pack turns the int32 selection into the byte buffer that
+    travels in its place.  Decode: _decode.  Returns the format that travelled ("auto" resolved; None: int32).
     Reference: sparse_hook.py:237-297 (and :363-410 for the large-batch hook)."""
     L = N.lib()
     input_tensor = bucket.buffer()
@@ -729,13 +767,16 @@ def _compress_exchange(state: SparseState, bucket, group, world_size: int, ef: i
                                           e_decay, dt, stream), "arctopk_sparse_residual")
 
     lay = (total, nt, a_off, a_k, a_ko)
-    packed = _idx16_pack(L, lay, indices, numels, stream) if idx16 else None  # the indices as they travel
+    # the indices as they travel: the format ("auto" resolved) and _exchange's tuple
+    idx16, packed = _index_pack(L, lay, indices, numels, idx16, stream) if idx16 else (None, None)
     vals, idx, nranks, accumulate = _exchange(state, group, world_size, values, indices, value_bits, count_bits,
                                               hashed=hashed, by_column=seg is not None and seg.by_column,
                                               idx16=packed)
     _decode(L, x, lay, sum_k, idx, vals, nranks, world_size, accumulate,
             state.global_error_dict[b].data_ptr() if ef == N.EF21 else None, g_decay, dt, stream, wire16=wire16,
-            scratch=src if mixed and ef == N.EF21 else None, wire_bytes=packed[0].numel() if idx16 else None)
+            scratch=src if mixed and ef == N.EF21 else None, idx16=idx16,
+            wire_bytes=packed[0].numel() if idx16 else None)
+    return idx16
 
 
 def _large_batch_ef21(state: SparseState, bucket, c4: bool) -> "torch.futures.Future[torch.Tensor]":

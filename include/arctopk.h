@@ -794,6 +794,75 @@ int arctopk_sparse_decode_idx16(void* out, int64_t numel, int32_t ntensors, cons
                                 int32_t val_dtype, int32_t nranks, int32_t world_size, void* gE,
                                 float decay, void* stream);
 
+/* ---- TopK baseline: indices as a per-tensor bitmap on the wire (SparseState.index_wire = "bitmap") ---- */
+/*
+ * Wire format "bitmap".  A layout is numel, ntensors, offsets, ks, k_off exactly as for "idx16"
+ * above: per tensor ascending, tensor-relative indices, n_i the tensor's extent,
+ * packed_len = k_off[last] + ks[last].  With
+ *   nw_i = ceil(n_i / 32),  nc_i = ceil(n_i / 4096),  wb_i = sum of nw_t, cb_i = sum of nc_t over t < i
+ * one rank's index payload is one byte buffer:
+ *   uint32 W[sum of nw_i]   bit e % 32 (LSB first) of W[wb_i + e / 32] is set iff element e of tensor
+ *                           i is selected; bits at or above n_i in a tensor's last word are zero
+ *   zero padding to the next multiple of 16
+ *   int32 C[sum of nc_i]    C[cb_i + c] = the number of tensor i's selected elements below c * 4096
+ *   zero padding to a multiple of 16
+ * Selected element e of tensor i has its value at
+ *   k_off[i] + C[cb_i + e / 4096] + (set bits of chunk e / 4096 below e).
+ * The size depends on the layout alone: sum of (n_i + 32 nc_i) information bits, which undercuts
+ * idx16's 16 per index above a ratio of about 0.063 and int32's 32 above about 0.032.  The group of
+ * 4096 elements is the chunk a decode block composes (csrc/sparse_chunk.h).
+ * Every entry below checks and refuses as its idx16 counterpart does, before any device call.
+ */
+
+/* Bytes of one rank's payload; -ARCTOPK_EINVAL for a layout as above. */
+int64_t arctopk_sparse_bitmap_bytes(int64_t numel, int32_t ntensors, const int64_t* offsets,
+                                    const int64_t* ks, const int64_t* k_off);
+
+/*
+ * idx (packed_len int32, each tensor's ascending) -> wire (arctopk_sparse_bitmap_bytes bytes, every
+ * byte written, padding included).  One launch per ARCTOPK_SPARSE_MAX_BATCH tensors, one pass: a
+ * block takes a span of consecutive 4096-element chunks of a tensor; a wave per chunk finds the
+ * lower bound of the chunk's first element in the tensor's indices (the chunk's table entry), the
+ * block sets the bits of the indices between the span's first and last bound in LDS and streams the
+ * span's words out (16-B nontemporal stores where the span's place in W is 16-B aligned).  No global
+ * atomic, no second pass.  An index outside its span is skipped; indices that do not ascend give an
+ * unspecified payload, never a store outside it.
+ */
+int arctopk_sparse_bitmap_pack(int64_t numel, int32_t ntensors, const int64_t* offsets,
+                               const int64_t* ks, const int64_t* k_off, const int32_t* idx, void* wire,
+                               void* stream);
+
+/*
+ * wire (nranks payloads, wire_stride_bytes apart) -> idx_out (nranks x packed_len int32): the
+ * format's inverse, for the decodes that read int32 indices.  Grid (chunk of a tensor, tensor,
+ * rank); a table entry is clamped to [0, ks], a position at or beyond ks is skipped and bits at or
+ * above n_i are masked, so a payload that holds anything writes inside idx_out only (entries no set
+ * bit lands on are left as they were).
+ * ARCTOPK_EINVAL also for nranks outside [1, 65535], packed_len other than the layout's, or a
+ * stride below the payload's bytes or not a multiple of 4.
+ */
+int arctopk_sparse_bitmap_unpack(int64_t numel, int32_t ntensors, const int64_t* offsets,
+                                 const int64_t* ks, const int64_t* k_off, int64_t packed_len,
+                                 const void* wire, int64_t wire_stride_bytes, int32_t nranks,
+                                 int32_t* idx_out, void* stream);
+
+/*
+ * Decode nranks bitmap payloads and their values into the fp32 bucket, every element written:
+ * arguments, per-element rule (s = 0.0f + v_0 + v_1 + ... in rank order, an element a rank did not
+ * select adding nothing; the mean; gE) and bits as arctopk_sparse_decode_idx16.  Block (x, y)
+ * composes chunk x of tensor y: per rank 128 lanes load the chunk's words and scan their
+ * popcounts, and the thread that owns an output element for all ranks adds the value at
+ * base + prefix + popcount(bits below) to a register.  A chunk whose place in out (and gE) is 16-B
+ * aligned is written as 16-B nontemporal units from registers, any other element by element.
+ * ARCTOPK_EINVAL also as arctopk_sparse_bitmap_unpack, for world_size < 1, another val_dtype, or
+ * offsets[0] != 0 (unpack, and decode as before).
+ */
+int arctopk_sparse_decode_bitmap(void* out, int64_t numel, int32_t ntensors, const int64_t* offsets,
+                                 const int64_t* ks, const int64_t* k_off, int64_t packed_len,
+                                 const void* wire, int64_t wire_stride_bytes, const void* vals,
+                                 int32_t val_dtype, int32_t nranks, int32_t world_size, void* gE,
+                                 float decay, void* stream);
+
 /*
  * Momentum fold of a whole bucket, in place, stream-ordered, one launch per
  * ARCTOPK_SPARSE_MAX_BATCH tensors: for every tensor i,
