@@ -114,6 +114,26 @@ __device__ __forceinline__ float energy_regs(const float (&acc)[R]) {
     return rnd<T>(s);
 }
 
+// V^T of a wave-per-row tile's columns [c0, c0 + cl) into LDS as fp32 [R][cl], and the barrier
+template <typename T, int R>
+__device__ __forceinline__ void stage_vt(float* __restrict__ lds, const T* __restrict__ Vs, int c0, int cl,
+                                         int tid) {
+    if constexpr (R == 4) {
+        for (int c = tid; c < cl; c += 256) {
+            const float4 v = ldq<T, false>(Vs, c0 + c);  // V[c0 + c][0..3]
+            lds[c] = v.x;
+            lds[cl + c] = v.y;
+            lds[2 * cl + c] = v.z;
+            lds[3 * cl + c] = v.w;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < R; ++j)
+            for (int c = tid; c < cl; c += 256) lds[j * cl + c] = to_f(Vs[(int64_t)(c0 + c) * R + j]);
+    }
+    __syncthreads();
+}
+
 // ZR (EF14 with E, err_in = ARCTOPK_ERR_IN_ZERO_ROWS): every row `zmap` (the plan's slot map)
 // marks selected (slot >= 0) is all zeros in E; the ENC_ROW_VEC tiles issue no loads from E for
 // such a row and add a register zero instead (the add itself stays: -0.0 in G comes out +0.0, as
@@ -286,6 +306,10 @@ __device__ __forceinline__ void encode_tile(const SegDev* __restrict__ segs, con
     // the sketch formed by v_dot2c_f32_bf16 (two products, exact in fp32, per instruction):
     // no unpacking of X and half the VALU instructions of the fp32-FMA form
     constexpr bool kDot2 = sizeof(T) == 2;
+    // the fp32 zero-rows kernel (2 waves per SIMD, registers to spare): a deeper ring of step
+    // buffers, and the walk's first loads issued ahead of the V^T staging and its barrier
+    constexpr bool kZr32 = ZR && !kDot2;
+    constexpr bool EARLY = kZr32 && ARCTOPK_ENC_ZR_EARLY;
     if (kDot2 && t.mode == ENC_ROW_VEC) {
         uint16_t* l16 = reinterpret_cast<uint16_t*>(lds);
 #pragma unroll
@@ -293,7 +317,7 @@ __device__ __forceinline__ void encode_tile(const SegDev* __restrict__ segs, con
             for (int c = tid; c < cl; c += 256)
                 l16[j * cl + c] = reinterpret_cast<const uint16_t*>(Vs)[(int64_t)(c0 + c) * R + j];
         __syncthreads();
-    } else {
+    } else if (!(EARLY && t.mode == ENC_ROW_VEC)) {  // (EARLY: stage_vt, after the walk's first loads)
         if constexpr (R == 4) {
             for (int c = tid; c < cl; c += 256) {
                 const float4 v = ldq<T, false>(Vs, c0 + c);  // V[c0 + c][0..3]
@@ -425,13 +449,16 @@ __device__ __forceinline__ void encode_tile(const SegDev* __restrict__ segs, con
     }
     if (t.mode == ENC_ROW_VEC) {
         // Software-pipelined stream: a wave walks its rows in steps of 64*U 16-B units
-        // (U per lane; a unit is 4 fp32 or 8 bf16 elements) with two register buffers: the
-        // loads of the next step are in flight while the current step forms its dot
-        // products, stores E and (at a row end) reduces.  V^T comes from LDS.
+        // (U per lane; a unit is 4 fp32 or 8 bf16 elements) with a ring of DEPTH register
+        // buffers: the loads of the next DEPTH - 1 steps are in flight while the current step
+        // forms its dot products, stores E and (at a row end) reduces.  V^T comes from LDS.
         constexpr int PQ = kQuadsPer16<T>;  // quads per 16-B unit
         constexpr bool LOAD_E = (EF == ARCTOPK_EF21) || (EF == ARCTOPK_EF14 && ERR_IN);
         // units per lane per step: a stream of G alone keeps more of them in flight
-        constexpr int U = (LOAD_E ? ARCTOPK_ENC_UNITS_GE : ARCTOPK_ENC_UNITS_G_ONLY) / PQ;
+        constexpr int U =
+            (kZr32 ? ARCTOPK_ENC_ZR_UNITS : LOAD_E ? ARCTOPK_ENC_UNITS_GE : ARCTOPK_ENC_UNITS_G_ONLY) / PQ;
+        constexpr int DEPTH = kZr32 ? ARCTOPK_ENC_ZR_DEPTH : 2;
+        static_assert(DEPTH >= 2 && U >= 1, "the row walk needs two step buffers of at least one unit");
         const int m4 = cl >> 2;   // quads of this tile row
         const int mu = m4 / PQ;   // 16-B units (the plan makes m4 a multiple of PQ)
         const int steps = (mu + 64 * U - 1) / (64 * U);
@@ -544,6 +571,33 @@ __device__ __forceinline__ void encode_tile(const SegDev* __restrict__ segs, con
         };
         // cursor over (tile row q, step) pairs of this wave: q = wave, wave + 4, ...
         const int64_t nq = t.nrows;
+        if constexpr (kZr32) {
+            // The same walk over a ring of DEPTH buffers, buffer d holding pair (rq[d], rst[d]).
+            // The ring is unrolled by DEPTH, so every buffer index is a constant: buffer d is
+            // consumed right after the pair DEPTH - 1 ahead of it went into buffer d - 1, the
+            // one consumed just before.  (At DEPTH 2 this is the walk below; written as this
+            // ring for every kernel it moved their register allocation)
+            float4 gr[DEPTH][U][PQ], er[DEPTH][U][PQ];
+            int64_t rq[DEPTH], qi = wave;
+            int rst[DEPTH], si = 0;
+            auto issue_next = [&](int d) {
+                rq[d] = qi;
+                rst[d] = si;
+                if (qi < nq) issue(gr[d], er[d], t.row0 + qi * rs, si, zrow(qi));
+                if (++si == steps) { si = 0; qi += 4; }
+            };
+#pragma unroll
+            for (int d = 0; d < DEPTH - 1; ++d) issue_next(d);
+            if constexpr (EARLY) stage_vt<T, R>(lds, Vs, c0, cl, tid);
+            while (true) {
+#pragma unroll
+                for (int d = 0; d < DEPTH; ++d) {
+                    if (rq[d] >= nq) return;
+                    issue_next((d + DEPTH - 1) % DEPTH);
+                    consume(gr[d], er[d], t.row0 + rq[d] * rs, rst[d]);
+                }
+            }
+        } else {
         int64_t qa = wave;
         int sa = 0;
         if (qa < nq) issue(ga, ea, t.row0 + qa * rs, sa, zrow(qa));
@@ -559,6 +613,7 @@ __device__ __forceinline__ void encode_tile(const SegDev* __restrict__ segs, con
             if (sa == steps) { sa = 0; qa += 4; }
             if (qa < nq) issue(ga, ea, t.row0 + qa * rs, sa, zrow(qa));
             consume(gb, eb, t.row0 + qb * rs, sb);
+        }
         }
     } else {  // ENC_ROW_SCALAR
         for (int64_t q = wave; q < t.nrows; q += 4) {
@@ -651,8 +706,10 @@ __device__ __forceinline__ void encode_zr_block(const SegDev* __restrict__ segs,
     encode_tile<T, R, ARCTOPK_EF14, true, true, true>(segs, tiles[blockIdx.x - pr.n], G, E, V, sketch, part_buf, keys,
                                                       lds, zmap);
 }
-// fp32: 170 VGPRs, 2 waves per SIMD where k_encode<float, 4, EF14, true> has 3 (164) -- left so:
-// held to 168 registers for the third wave it measured slower
+// fp32: 2 waves per SIMD where k_encode<float, 4, EF14, true> has 3 (164 VGPRs) -- left so: held
+// to 168 registers for the third wave it measured slower.  At 2 waves a wave may hold
+// 256 VGPRs, so its row walk keeps a ring of ARCTOPK_ENC_ZR_DEPTH step buffers (202 VGPRs at 3)
+// and issues the ring's first loads ahead of the V^T staging (ARCTOPK_ENC_ZR_EARLY)
 // (the two are told apart by the order of their template parameters: plain names that every
 // profiler demangles)
 template <typename T, int R, typename Z>

@@ -79,6 +79,16 @@
 #ifndef ARCTOPK_ENC_UNITS_GE
 #define ARCTOPK_ENC_UNITS_GE 4         // fp32 encode with E loads: 16-B units of G (and of E) per lane per step
 #endif
+// the fp32 zero-rows encode (k_encode<float, R, ZeroRows>: 2 waves per SIMD, so up to 256 VGPRs a wave)
+#ifndef ARCTOPK_ENC_ZR_DEPTH
+#define ARCTOPK_ENC_ZR_DEPTH 3         // step buffers of its row walk: DEPTH - 1 steps' loads in flight (2 elsewhere)
+#endif
+#ifndef ARCTOPK_ENC_ZR_UNITS
+#define ARCTOPK_ENC_ZR_UNITS ARCTOPK_ENC_UNITS_GE  // its 16-B units of G (and of E) per lane per step
+#endif
+#ifndef ARCTOPK_ENC_ZR_EARLY
+#define ARCTOPK_ENC_ZR_EARLY 1         // its first DEPTH - 1 steps' loads issued before the V^T staging and barrier
+#endif
 #ifndef ARCTOPK_ENC_UNITS_BF16
 #define ARCTOPK_ENC_UNITS_BF16 4       // bf16 encode rows: 16-B units per lane per step
 #endif

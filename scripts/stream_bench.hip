@@ -2,6 +2,7 @@
 // read/write mixes of the codec's phases (encode EF14: read G, E, write E in place).
 //   hipcc --offload-arch=gfx950 -O3 scripts/stream_bench.hip -o scripts/stream_bench
 //   ./scripts/stream_bench [MiB per array] [sets]
+//   ./scripts/stream_bench 256 4 ring      (the ring-depth probe of the row-shaped add alone)
 //
 // Two regimes per kernel: "warm" repeats the kernel on ONE set of arrays (what earlier rounds
 // quoted: 2-3 x 256 MiB fit the 256 MB Infinity Cache (MALL) in part, so repeats find some of
@@ -14,6 +15,7 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <string>
 #include <vector>
 
 #define CK(x)                                                                              \
@@ -91,6 +93,47 @@ __global__ void __launch_bounds__(256) k_rows(const float4* __restrict__ a, floa
                 const size_t j = row + st * 64 * U + u * 64 + lane;
                 st_nt(b + j, make_float4(x[u].x + y[u].x, x[u].y + y[u].y, x[u].z + y[u].z, x[u].w + y[u].w));
             }
+        }
+    }
+}
+
+// k_rows with the encode's software pipeline: a ring of DEPTH step buffers over the wave's (row,
+// step) pairs, DEPTH - 1 steps' loads (U units of a and of b each) in flight while one step is
+// added and stored; held to 2 waves per SIMD, the occupancy of the fp32 zero-rows encode
+template <int U, int DEPTH>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
+k_rows_ring(const float4* __restrict__ a, float4* __restrict__ b, int rows, int ntiles) {
+    constexpr int MU = 512, STEPS = MU / (64 * U);
+    const int t = blockIdx.x / ntiles, ti = blockIdx.x % ntiles;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int nr = (rows - ti + ntiles - 1) / ntiles;
+    const size_t base = (size_t)t * rows * MU;
+    float4 x[DEPTH][U], y[DEPTH][U];
+    int rq[DEPTH], rst[DEPTH], qi = wave, si = 0;
+    auto unit = [&](int q, int st, int u) { return base + (size_t)(ti + q * ntiles) * MU + st * 64 * U + u * 64 + lane; };
+    auto issue_next = [&](int d) {
+        rq[d] = qi;
+        rst[d] = si;
+        if (qi < nr) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                x[d][u] = ld_nt(a + unit(qi, si, u));
+                y[d][u] = ld_nt(b + unit(qi, si, u));
+            }
+        }
+        if (++si == STEPS) { si = 0; qi += 4; }
+    };
+#pragma unroll
+    for (int d = 0; d < DEPTH - 1; ++d) issue_next(d);
+    while (true) {
+#pragma unroll
+        for (int d = 0; d < DEPTH; ++d) {
+            if (rq[d] >= nr) return;
+            issue_next((d + DEPTH - 1) % DEPTH);
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                st_nt(b + unit(rq[d], rst[d], u), make_float4(x[d][u].x + y[d][u].x, x[d][u].y + y[d][u].y,
+                                                             x[d][u].z + y[d][u].z, x[d][u].w + y[d][u].w));
         }
     }
 }
@@ -185,6 +228,28 @@ int main(int argc, char** argv) {
     const double bytes = (double)n * 4;
     const int reps = 24;
     std::printf("%zu MiB per array, %d sets (cold: every launch on the next set)\n", mib, sets);
+    if (argc > 3 && std::string(argv[3]) == "ring") {
+        // the ring-depth probe alone: cold, the encode's row shape, 256 tiles per tensor (4,096 blocks)
+        if (mib != 256) return 1;
+        auto run = [&](const char* name, auto kern) {
+            std::printf("cold rows, ring %-18s:", name);
+            for (int rep = 0; rep < 3; ++rep) {
+                const float tw = time_it([&](int i) {
+                    hipLaunchKernelGGL(kern, dim3(16 * 256), dim3(256), 0, 0, (const float4*)A[i % sets],
+                                       (float4*)B[i % sets], 2048, 256); }, reps);
+                std::printf("  %5.0f GB/s %6.1f us", 3 * bytes / tw / 1e6, tw * 1e3);
+            }
+            std::printf("\n");
+        };
+        for (int round = 0; round < 2; ++round) {
+            run("none (k_rows<4>)", k_rows<4>);
+            run("U 4 depth 2", k_rows_ring<4, 2>);
+            run("U 4 depth 3", k_rows_ring<4, 3>);
+            run("U 4 depth 4", k_rows_ring<4, 4>);
+            run("U 8 depth 2", k_rows_ring<8, 2>);
+        }
+        return 0;
+    }
     for (int cold = 0; cold < 2; ++cold) {
         auto pick = [&](int i) { return cold ? i % sets : 0; };
         for (unsigned g : {1024u, 2048u, 4096u, 8192u, 16384u}) {
