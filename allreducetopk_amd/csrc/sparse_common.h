@@ -1,4 +1,5 @@
-// What sparse_kernels.hip, sparse_mixed.hip and sparse_idx16.hip share.
+// What sparse_kernels.hip, sparse_mixed.hip, sparse_idx16.hip and sparse_bitmap.hip share (the last two
+// through sparse_index_wire.h as well).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -78,6 +79,18 @@ int fill_batches(Batches& bs, int32_t nt, int64_t numel, const int64_t* offsets,
         if (packed_len >= 0 && b.koff[i] + b.k[i] > packed_len) return ARCTOPK_EINVAL;
         bs.maxk[t / kB] = std::max(bs.maxk[t / kB], b.k[i]);
         bs.maxn[t / kB] = std::max(bs.maxn[t / kB], b.n[i]);
+    }
+    return 0;
+}
+
+// launch(q) for every batch q in order; the first launch that leaves an error ends the loop, and that
+// error is returned
+template <typename Launch>
+int launch_batches(const Batches& bs, Launch launch) {
+    for (size_t q = 0; q < bs.b.size(); ++q) {
+        launch(q);
+        const int e = (int)hipGetLastError();
+        if (e) return e;
     }
     return 0;
 }

@@ -30,6 +30,7 @@
 #include "mixed_common.h"
 #include "sparse_chunk.h"
 #include "sparse_common.h"
+#include "sparse_index_wire.h"
 
 namespace {
 
@@ -251,90 +252,53 @@ __global__ void __launch_bounds__(256) k_decode_idx16(MixedBatch b, Idx16Batch x
 }
 
 // ---- host ----------------------------------------------------------------------------------
-inline int64_t up16(int64_t bytes) { return (bytes + 15) & ~(int64_t)15; }
-
-// The checked layout and the format's geometry: table_off, the byte offset of T; bytes, one rank's
-// whole payload.  ARCTOPK_EINVAL as fill_batches.
-struct Idx16Layout {
-    Batches bs;
-    std::vector<Idx16Batch> xb;
-    int64_t packed_len, sum_nb, table_off, bytes;
-};
-
-int idx16_layout(Idx16Layout& L, int64_t numel, int32_t nt, const int64_t* offsets, const int64_t* ks,
-                 const int64_t* k_off) {
-    if (!offsets || !ks || !k_off || nt < 1 || numel < 1) return ARCTOPK_EINVAL;
-    L.packed_len = k_off[nt - 1] + ks[nt - 1];
-    const int e = fill_batches(L.bs, nt, numel, offsets, ks, k_off, L.packed_len);
-    if (e) return e;
-    L.xb.assign(L.bs.b.size(), Idx16Batch{});
-    L.sum_nb = 0;
-    for (int32_t t = 0; t < nt; ++t) {
-        L.xb[t / kB].tb[t % kB] = L.sum_nb;
-        L.sum_nb += (L.bs.b[t / kB].n[t % kB] + (1 << kBlockBits) - 1) >> kBlockBits;
+// The format for the shared driver (sparse_index_wire.h): the body is lo16, packed_len halves; the table
+// is T, a tensor's blocks at tb.
+struct Idx16Wire {
+    using Batch = Idx16Batch;
+    using Body = uint16_t;
+    static void place(WireLayout<Batch>& L, int64_t& body, int64_t& table) {
+        for (int32_t t = 0; t < L.bs.nt; ++t) {
+            L.xb[t / kB].tb[t % kB] = table;
+            table += (L.bs.b[t / kB].n[t % kB] + (1 << kBlockBits) - 1) >> kBlockBits;
+        }
+        body = L.packed_len;
     }
-    L.table_off = up16(2 * L.packed_len);
-    L.bytes = L.table_off + up16(4 * L.sum_nb);
-    Idx16Batch& x0 = L.xb[0];
-    x0.pad_lo = L.packed_len;
-    x0.n_pad_lo = (int32_t)(L.table_off / 2 - L.packed_len);
-    x0.pad_t = L.sum_nb;
-    x0.n_pad_t = (int32_t)((L.bytes - L.table_off) / 4 - L.sum_nb);
-    return 0;
-}
-
-// what the two readers check of the gathered payloads
-int idx16_wire_ok(const Idx16Layout& L, int64_t packed_len, const void* wire, int64_t stride, int32_t nranks) {
-    if (!wire || arctopk::low_bits(wire, 3) || nranks < 1 || nranks > 65535) return ARCTOPK_EINVAL;
-    if (packed_len != L.packed_len || stride < L.bytes || (stride & 3)) return ARCTOPK_EINVAL;
-    return 0;
-}
+    static void pads(Batch& x0, int64_t body, int32_t n_body, int64_t table, int32_t n_table) {
+        x0.pad_lo = body, x0.n_pad_lo = n_body;
+        x0.pad_t = table, x0.n_pad_t = n_table;
+    }
+    static unsigned pack_grid_x(const Batches& bs, size_t q) {
+        const int64_t steps = (bs.maxk[q] + 8 * 256 * kUnits - 1) / (8 * 256 * kUnits);
+        return (unsigned)std::max<int64_t>(1, std::min<int64_t>(2048, steps));
+    }
+    static unsigned unpack_grid_x(const Batches& bs, size_t q) {
+        return (unsigned)((bs.maxn[q] + (1 << kBlockBits) - 1) >> kBlockBits);
+    }
+    static constexpr auto pack_kernel = k_idx16_pack;
+    static constexpr auto unpack_kernel = k_idx16_unpack;
+    template <bool GE, typename V>
+    static constexpr auto decode_kernel = k_decode_idx16<GE, V>;
+};
 
 }  // namespace
 
 extern "C" int64_t arctopk_sparse_idx16_bytes(int64_t numel, int32_t nt, const int64_t* offsets, const int64_t* ks,
                                               const int64_t* k_off) {
-    Idx16Layout L;
-    const int e = idx16_layout(L, numel, nt, offsets, ks, k_off);
-    return e ? -(int64_t)e : L.bytes;
+    return wire_bytes<Idx16Wire>(numel, nt, offsets, ks, k_off);
 }
 
 extern "C" int arctopk_sparse_idx16_pack(int64_t numel, int32_t nt, const int64_t* offsets, const int64_t* ks,
                                          const int64_t* k_off, const int32_t* idx, void* wire, void* stream) {
-    if (!idx || !wire || arctopk::low_bits(idx, 3) || arctopk::low_bits(wire, 3)) return ARCTOPK_EINVAL;
-    Idx16Layout L;
-    const int e0 = idx16_layout(L, numel, nt, offsets, ks, k_off);
-    if (e0) return e0;
-    uint16_t* lo16 = static_cast<uint16_t*>(wire);
-    int32_t* T = reinterpret_cast<int32_t*>(static_cast<uint8_t*>(wire) + L.table_off);
-    for (size_t q = 0; q < L.bs.b.size(); ++q) {
-        const int64_t steps = (L.bs.maxk[q] + 8 * 256 * kUnits - 1) / (8 * 256 * kUnits);
-        const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(2048, steps)), L.bs.count(q));
-        hipLaunchKernelGGL(k_idx16_pack, grid, dim3(256), 0, (hipStream_t)stream, L.bs.b[q], L.xb[q], idx, lo16, T);
-        const int e = (int)hipGetLastError();
-        if (e) return e;
-    }
-    return 0;
+    return wire_pack<Idx16Wire>(numel, nt, offsets, ks, k_off, idx, wire, stream);
 }
 
 extern "C" int arctopk_sparse_idx16_unpack(int64_t numel, int32_t nt, const int64_t* offsets, const int64_t* ks,
                                            const int64_t* k_off, int64_t packed_len, const void* wire,
                                            int64_t wire_stride_bytes, int32_t nranks, int32_t* idx_out,
                                            void* stream) {
-    if (!idx_out || arctopk::low_bits(idx_out, 3)) return ARCTOPK_EINVAL;
-    Idx16Layout L;
-    const int e0 = idx16_layout(L, numel, nt, offsets, ks, k_off);
-    if (e0) return e0;
-    const int e1 = idx16_wire_ok(L, packed_len, wire, wire_stride_bytes, nranks);
-    if (e1) return e1;
-    for (size_t q = 0; q < L.bs.b.size(); ++q) {
-        const dim3 grid((unsigned)((L.bs.maxn[q] + (1 << kBlockBits) - 1) >> kBlockBits), L.bs.count(q), nranks);
-        hipLaunchKernelGGL(k_idx16_unpack, grid, dim3(256), 0, (hipStream_t)stream, L.bs.b[q], L.xb[q],
-                           static_cast<const uint8_t*>(wire), wire_stride_bytes, L.table_off, packed_len, idx_out);
-        const int e = (int)hipGetLastError();
-        if (e) return e;
-    }
-    return 0;
+    return wire_unpack<Idx16Wire>(numel, nt, offsets, ks, k_off, packed_len, wire, wire_stride_bytes, nranks, idx_out,
+                                  stream);
 }
 
 extern "C" int arctopk_sparse_decode_idx16(void* out, int64_t numel, int32_t nt, const int64_t* offsets,
@@ -342,39 +306,6 @@ extern "C" int arctopk_sparse_decode_idx16(void* out, int64_t numel, int32_t nt,
                                            const void* wire, int64_t wire_stride_bytes, const void* vals,
                                            int32_t val_dtype, int32_t nranks, int32_t world_size, void* gE,
                                            float decay, void* stream) {
-    if (!out || !vals || world_size < 1 || (val_dtype != ARCTOPK_F32 && val_dtype != ARCTOPK_BF16))
-        return ARCTOPK_EINVAL;
-    if (arctopk::low_bits(out, 3) || arctopk::low_bits(gE, 3) ||
-        arctopk::low_bits(vals, val_dtype == ARCTOPK_F32 ? 3 : 1))
-        return ARCTOPK_EINVAL;
-    Idx16Layout L;
-    const int e0 = idx16_layout(L, numel, nt, offsets, ks, k_off);
-    if (e0) return e0;
-    const int e1 = idx16_wire_ok(L, packed_len, wire, wire_stride_bytes, nranks);
-    if (e1) return e1;
-    // the tensors tile [offsets[0], numel) in order (fill_batches); only from 0 do the chunks cover
-    // the bucket, and every element has to be written
-    if (offsets[0] != 0) return ARCTOPK_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    float* o = static_cast<float*>(out);
-    float* ge = static_cast<float*>(gE);
-    const uint8_t* w = static_cast<const uint8_t*>(wire);
-    const MeanScale sc = arctopk::make_mean_scale(world_size);
-    for (size_t q = 0; q < L.bs.b.size(); ++q) {
-        const dim3 grid((unsigned)((L.bs.maxn[q] + kChunk - 1) / kChunk), L.bs.count(q));
-#define ARCTOPK_IDX16_DECODE(GE, V)                                                                              \
-    hipLaunchKernelGGL((k_decode_idx16<GE, V>), grid, dim3(256), 0, st, L.bs.b[q], L.xb[q], o, ge, w,             \
-                       wire_stride_bytes, L.table_off, static_cast<const V*>(vals), nranks, packed_len, sc, decay)
-        if (val_dtype == ARCTOPK_F32) {
-            if (ge) ARCTOPK_IDX16_DECODE(true, float);
-            else ARCTOPK_IDX16_DECODE(false, float);
-        } else {
-            if (ge) ARCTOPK_IDX16_DECODE(true, uint16_t);
-            else ARCTOPK_IDX16_DECODE(false, uint16_t);
-        }
-#undef ARCTOPK_IDX16_DECODE
-        const int e = (int)hipGetLastError();
-        if (e) return e;
-    }
-    return 0;
+    return wire_decode<Idx16Wire>(out, numel, nt, offsets, ks, k_off, packed_len, wire, wire_stride_bytes, vals,
+                                  val_dtype, nranks, world_size, gE, decay, stream);
 }

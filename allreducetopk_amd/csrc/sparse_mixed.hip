@@ -399,13 +399,12 @@ int scatter_ranks(const Batches& bs, float* sums, const int32_t* idx, const uint
     for (int32_t r = 0; r < nranks; ++r) {
         const int32_t* ir = idx + (int64_t)r * packed_len;
         const uint16_t* vr = vals + (int64_t)r * packed_len;
-        for (size_t q = 0; q < bs.b.size(); ++q) {
+        const int e = launch_batches(bs, [&](size_t q) {
             const dim3 grid(gather_grid(bs.maxk[q]), bs.count(q));
             if (r == 0) hipLaunchKernelGGL(k_scatter<true>, grid, dim3(256), 0, st, bs.b[q], sums, ir, vr);
             else hipLaunchKernelGGL(k_scatter<false>, grid, dim3(256), 0, st, bs.b[q], sums, ir, vr);
-            const int e = (int)hipGetLastError();
-            if (e) return e;
-        }
+        });
+        if (e) return e;
     }
     return 0;
 }
@@ -456,16 +455,13 @@ extern "C" int arctopk_sparse_pack_mixed(const void* src, void* E, int64_t numel
     const float* s = static_cast<const float*>(src);
     float* Ef = static_cast<float*>(E);
     uint16_t* v = static_cast<uint16_t*>(vals);
-    for (size_t q = 0; q < bs.b.size(); ++q) {
+    return launch_batches(bs, [&](size_t q) {
         const dim3 grid(gather_grid(bs.maxk[q]), bs.count(q));
         if (ef == ARCTOPK_EF14)
             hipLaunchKernelGGL(k_pack<ARCTOPK_EF14>, grid, dim3(256), 0, st, bs.b[q], s, Ef, idx, v, decay);
         else
             hipLaunchKernelGGL(k_pack<ARCTOPK_EF21>, grid, dim3(256), 0, st, bs.b[q], s, Ef, idx, v, decay);
-        const int e = (int)hipGetLastError();
-        if (e) return e;
-    }
-    return 0;
+    });
 }
 
 extern "C" int arctopk_sparse_decode_mixed21(void* out, void* gE, void* scratch, int64_t numel, int32_t nt,
@@ -517,7 +513,7 @@ extern "C" int arctopk_sparse_pack_wire16(const void* values, void* E, int64_t n
     float* Ef = static_cast<float*>(E);
     uint16_t* o = static_cast<uint16_t*>(vals16);
     const int aligned16 = !arctopk::low_bits(values, 15) && !arctopk::low_bits(idx, 15) && !arctopk::low_bits(vals16, 7);
-    for (size_t q = 0; q < bs.b.size(); ++q) {
+    return launch_batches(bs, [&](size_t q) {
         const dim3 grid(gather_grid((bs.maxk[q] + 3) / 4), bs.count(q));
         if (ef == ARCTOPK_EF14)
             hipLaunchKernelGGL(k_pack16<ARCTOPK_EF14>, grid, dim3(256), 0, st, bs.b[q], v, Ef, idx, o, decay, aligned16);
@@ -526,10 +522,7 @@ extern "C" int arctopk_sparse_pack_wire16(const void* values, void* E, int64_t n
         else
             hipLaunchKernelGGL(k_pack16<ARCTOPK_EF_NONE>, grid, dim3(256), 0, st, bs.b[q], v, Ef, idx, o, decay,
                                aligned16);
-        const int e = (int)hipGetLastError();
-        if (e) return e;
-    }
-    return 0;
+    });
 }
 
 extern "C" int arctopk_sparse_decode_wire16(void* out, int64_t numel, int32_t nt, const int64_t* offsets,
@@ -554,7 +547,7 @@ extern "C" int arctopk_sparse_decode_wire16(void* out, int64_t numel, int32_t nt
     const int nr = ranked ? nranks : 1;  // RandK: the one all-reduced payload
     // the tensors tile [offsets[0], numel) in order (fill_batches); from 0, the chunks cover the bucket
     if ((accumulate == 1 || accumulate == 2) && offsets[0] == 0) {
-        for (size_t q = 0; q < bs.b.size(); ++q) {
+        return launch_batches(bs, [&](size_t q) {
             const dim3 grid((unsigned)((bs.maxn[q] + kChunk - 1) / kChunk), bs.count(q));
             if (ge)
                 hipLaunchKernelGGL(k_decode_merged<true>, grid, dim3(256), 0, st, bs.b[q], o, ge, idx, v, nr,
@@ -562,10 +555,7 @@ extern "C" int arctopk_sparse_decode_wire16(void* out, int64_t numel, int32_t nt
             else
                 hipLaunchKernelGGL(k_decode_merged<false>, grid, dim3(256), 0, st, bs.b[q], o, ge, idx, v, nr,
                                    packed_len, sc, decay);
-            const int e = (int)hipGetLastError();
-            if (e) return e;
-        }
-        return 0;
+        });
     }
     hipError_t he = hipMemsetAsync(o, 0, (size_t)numel * sizeof(float), st);
     if (he != hipSuccess) return (int)he;

@@ -15,8 +15,8 @@ import sparse_bitmap_format as F
 from allreducetopk_amd import _native as N
 from allreducetopk_amd.bucket import bucket_numel
 from parity import rendezvous
-from test_gpu_sparse_idx16 import (BF16, CONFIGS, F32, HERE, MIX, MIX_2D, REPO, SM, S, _args, _call, _grad, _guarded,
-                                   _intact, _restatement, _same_bits, _state, _stream, _want,
+from test_gpu_sparse_idx16 import (BF16, CONFIGS, F32, HERE, MIX, MIX_2D, REPO, SM, S, _args, _bad_wire_args, _call, _grad,
+                                   _guarded, _intact, _restatement, _same_bits, _state, _stream, _want,
                                    group)  # noqa: F401  (the module's process group fixture)
 
 pytestmark = pytest.mark.gpu
@@ -32,7 +32,10 @@ def _case(name):
         shapes, *idxs = hand[name]
         return shapes, [len(i) for i in idxs], [torch.tensor(i, dtype=torch.int32) for i in idxs]
     shapes, ratio = {"edge": ([[31], [32], [33], [C - 1], [C], [C + 1], [2 * C + 1]], 0.25), "full": ([[C + 1]], 1.0),
-                     "mix": (MIX, 0.25), "many": ([[33]] * 70, 0.25), "one": ([[1]], 0.25)}[name]
+                     "mix": (MIX, 0.25), "many": ([[33]] * 70, 0.25), "one": ([[1]], 0.25),
+                     # ARCTOPK_SPARSE_MAX_BATCH + 1 tensors, so two launches per entry; a tensor that crosses an
+                     # idx16 block in the first batch, one that crosses a chunk alone in the second
+                     "batches": ([[33]] * 63 + [[65537], [C + 1]], 0.25)}[name]
     X = _grad(bucket_numel(shapes), 5)
     return shapes, SM.layout_ks(shapes, ratio, "tensor"), SM.select(X, shapes, ratio, "tensor", False, "host", None)
 
@@ -42,7 +45,7 @@ def _encode(shapes, ks, idxs):
 
 
 @pytest.mark.parametrize("shift", [0, 1])
-@pytest.mark.parametrize("name", ["edge", "full", "hand", "late", "mix", "many", "one"])
+@pytest.mark.parametrize("name", ["edge", "full", "hand", "late", "mix", "many", "one", "batches"])
 def test_pack_then_unpack(name, shift):
     shapes, ks, idxs = _case(name)
     _, lay = _args(shapes, ks)
@@ -54,12 +57,22 @@ def test_pack_then_unpack(name, shift):
         N.check(N.lib().arctopk_sparse_bitmap_pack(*lay, idx_d.data_ptr(), wire_d.data_ptr() + r * stride, _stream()),
                 "arctopk_sparse_bitmap_pack")
     obuf, out_d = _guarded(torch.full((2 * sum(ks),), -7, dtype=torch.int32), shift)
-    N.check(N.lib().arctopk_sparse_bitmap_unpack(*lay, sum(ks), wire_d.data_ptr(), stride, 2, out_d.data_ptr(), _stream()),
-            "arctopk_sparse_bitmap_unpack")
+
+    def unpack(lay=lay, packed_len=sum(ks), wire=wire_d.data_ptr(), stride=stride, nranks=2):
+        return N.lib().arctopk_sparse_bitmap_unpack(*lay, packed_len, wire, stride, nranks, out_d.data_ptr(), _stream())
+    for bad in _bad_wire_args(sum(ks), wire_d.data_ptr(), want.numel()):
+        assert unpack(**bad) == N.EINVAL, bad
+    torch.cuda.synchronize()
+    assert bool((out_d == -7).all())  # a refusal launches nothing
+    N.check(unpack(), "arctopk_sparse_bitmap_unpack")
     torch.cuda.synchronize()
     got = wire_d.cpu().view(2, stride)
     assert torch.equal(got[:, :want.numel()], want.expand(2, -1)) and bool((got[:, want.numel():] == 0x5A).all())
     assert torch.equal(out_d.cpu(), idx.repeat(2)) and torch.equal(idx_d.cpu(), idx)
+    out_d.fill_(-7)
+    N.check(unpack(lay=_args(shapes, ks, first=8)[1]), "arctopk_sparse_bitmap_unpack")  # only a decode needs offsets[0] == 0
+    torch.cuda.synchronize()
+    assert torch.equal(out_d.cpu(), idx.repeat(2))
     assert _intact(ibuf, idx_d) and _intact(wbuf, wire_d) and _intact(obuf, out_d)
 
 
@@ -78,16 +91,25 @@ def _draws(name, nranks):
     return shapes, ks, all_idx, all_vals
 
 
-def _decode(shapes, ks, wires, vals, nranks, gE0, decay, shift=0):
-    """One arctopk_sparse_decode_bitmap between guards: (out, gE) on the CPU."""
+def _decode(shapes, ks, wires, vals, nranks, gE0, decay, shift=0, gap=0):
+    """One arctopk_sparse_decode_bitmap between guards, the payloads `gap` bytes apart, behind the calls it has to
+    refuse (which launch nothing): (out, gE) on the CPU."""
     numels, lay = _args(shapes, ks)
     obuf, out_d = _guarded(torch.full((sum(numels),), 5.0), shift)
     gbuf, gE_d = _guarded(gE0, shift) if gE0 is not None else (None, None)
-    wbuf, wire_d = _guarded(torch.cat(wires))
+    wbuf, wire_d = _guarded(torch.cat([torch.cat([w, torch.full((gap,), 0x5A, dtype=torch.uint8)]) for w in wires]))
     vbuf, vals_d = _guarded(torch.cat(vals))
-    N.check(N.lib().arctopk_sparse_decode_bitmap(out_d.data_ptr(), *lay, sum(ks), wire_d.data_ptr(), wires[0].numel(),
-                                                 vals_d.data_ptr(), N.DTYPE_CODE[vals[0].dtype], nranks, nranks,
-                                                 N.ptr(gE_d), decay, _stream()), "arctopk_sparse_decode_bitmap")
+
+    def decode(lay=lay, packed_len=sum(ks), wire=wire_d.data_ptr(), stride=wires[0].numel() + gap, nranks=nranks):
+        return N.lib().arctopk_sparse_decode_bitmap(out_d.data_ptr(), *lay, packed_len, wire, stride, vals_d.data_ptr(),
+                                                    N.DTYPE_CODE[vals[0].dtype], nranks, len(wires), N.ptr(gE_d), decay,
+                                                    _stream())
+    refused = _bad_wire_args(sum(ks), wire_d.data_ptr(), wires[0].numel()) + [dict(lay=_args(shapes, ks, first=8)[1])]
+    for bad in refused:
+        assert decode(**bad) == N.EINVAL, bad
+    torch.cuda.synchronize()
+    assert bool((out_d == 5.0).all()) and (gE_d is None or torch.equal(gE_d.cpu(), gE0))
+    N.check(decode(), "arctopk_sparse_decode_bitmap")
     torch.cuda.synchronize()
     assert _intact(obuf, out_d) and _intact(wbuf, wire_d) and _intact(vbuf, vals_d)
     assert gE_d is None or _intact(gbuf, gE_d)
@@ -97,7 +119,7 @@ def _decode(shapes, ks, wires, vals, nranks, gE0, decay, shift=0):
 @pytest.mark.parametrize("decay", [None, 0.7])
 @pytest.mark.parametrize("vdtype", [F32, BF16])
 @pytest.mark.parametrize("nr", [1, 2, 3])
-@pytest.mark.parametrize("name", ["edge", "hand", "mix"])
+@pytest.mark.parametrize("name", ["edge", "hand", "mix", "batches"])
 def test_decode_phase(name, nr, vdtype, decay):
     shapes, ks, all_idx, all_vals = _draws(name, nr)
     all_vals = [v.to(vdtype) for v in all_vals]
@@ -106,7 +128,8 @@ def test_decode_phase(name, nr, vdtype, decay):
     if decay is not None:
         gE0 = _grad(bucket_numel(shapes), 9, 0.37)
         gE0[::5] = -0.0
-    out, gE = _decode(shapes, ks, wires, all_vals, nr, gE0, decay or 1.0, shift=int(name == "mix"))
+    out, gE = _decode(shapes, ks, wires, all_vals, nr, gE0, decay or 1.0, shift=int(name == "mix"),
+                      gap=16 * (name == "batches"))
     want_out, want_gE = _want(shapes, ks, all_idx, all_vals, nr, gE0, decay or 1.0)
     _same_bits(out, want_out, f"{name}/{nr}/{vdtype} out")
     if gE0 is not None:

@@ -42,7 +42,10 @@ def _case(name):
         shapes, *idxs = hand[name]
         return shapes, [len(i) for i in idxs], [torch.tensor(i, dtype=torch.int32) for i in idxs]
     shapes, ratio = {"edge": ([[B - 1], [B], [B + 1], [2 * B + 1]], 0.25), "full": ([[B + 1]], 1.0), "mix": (MIX, 0.25),
-                     "many": ([[33]] * 70, 0.25), "one": ([[1]], 0.25)}[name]
+                     "many": ([[33]] * 70, 0.25), "one": ([[1]], 0.25),
+                     # ARCTOPK_SPARSE_MAX_BATCH + 1 tensors, so two launches per entry; a tensor that crosses a block
+                     # in the first batch, one that crosses a bitmap chunk alone in the second
+                     "batches": ([[33]] * 63 + [[B + 1], [4097]], 0.25)}[name]
     X = _grad(bucket_numel(shapes), 5)
     return shapes, SM.layout_ks(shapes, ratio, "tensor"), SM.select(X, shapes, ratio, "tensor", False, "host", None)
 
@@ -61,14 +64,23 @@ def _intact(buf, view):
     return bool((buf[:lo] == buf[0]).all() and (buf[lo + view.numel():] == buf[0]).all())
 
 
-def _args(shapes, ks):
+def _args(shapes, ks, first=0):
+    """(numels, the entries' layout arguments); the tensors tile [first, first + sum(numels))."""
     numels = [S.numel_of(s) for s in shapes]
-    arrays = [N.i64_array([sum(v[:i]) for i in range(len(v))]) for v in (numels, ks)]
-    return numels, (sum(numels), len(shapes), arrays[0], N.i64_array(ks), arrays[1])
+    offs, koff = ([base + sum(v[:i]) for i in range(len(v))] for base, v in ((first, numels), (0, ks)))
+    return numels, (first + sum(numels), len(shapes), N.i64_array(offs), N.i64_array(ks), N.i64_array(koff))
+
+
+def _bad_wire_args(sum_k, wire, nbytes):
+    """What both readers refuse of the gathered payloads (`nbytes` each, a multiple of 16), one argument at a
+    time: a misaligned wire, a stride that is no multiple of 4, a stride below the payload, no rank, more
+    ranks than a grid's z takes, another packed_len."""
+    return [dict(wire=wire + 2), dict(stride=nbytes + 2), dict(stride=nbytes - 4), dict(nranks=0), dict(nranks=65536),
+            dict(packed_len=sum_k + 1)]
 
 
 @pytest.mark.parametrize("shift", [0, 1])
-@pytest.mark.parametrize("name", ["edge", "full", "hand", "late", "mix", "many", "one"])
+@pytest.mark.parametrize("name", ["edge", "full", "hand", "late", "mix", "many", "one", "batches"])
 def test_pack_then_unpack(name, shift):
     shapes, ks, idxs = _case(name)
     numels, lay = _args(shapes, ks)
@@ -81,12 +93,22 @@ def test_pack_then_unpack(name, shift):
         N.check(N.lib().arctopk_sparse_idx16_pack(*lay, idx_d.data_ptr(), wire_d.data_ptr() + r * stride, _stream()),
                 "arctopk_sparse_idx16_pack")
     obuf, out_d = _guarded(torch.full((2 * sum(ks),), -7, dtype=torch.int32), shift)
-    N.check(N.lib().arctopk_sparse_idx16_unpack(*lay, sum(ks), wire_d.data_ptr(), stride, 2, out_d.data_ptr(), _stream()),
-            "arctopk_sparse_idx16_unpack")
+
+    def unpack(lay=lay, packed_len=sum(ks), wire=wire_d.data_ptr(), stride=stride, nranks=2):
+        return N.lib().arctopk_sparse_idx16_unpack(*lay, packed_len, wire, stride, nranks, out_d.data_ptr(), _stream())
+    for bad in _bad_wire_args(sum(ks), wire_d.data_ptr(), want.numel()):
+        assert unpack(**bad) == N.EINVAL, bad
+    torch.cuda.synchronize()
+    assert bool((out_d == -7).all())  # a refusal launches nothing
+    N.check(unpack(), "arctopk_sparse_idx16_unpack")
     torch.cuda.synchronize()
     got = wire_d.cpu().view(2, stride)
     assert torch.equal(got[:, :want.numel()], want.expand(2, -1)) and bool((got[:, want.numel():] == 0x5A).all())
     assert torch.equal(out_d.cpu(), idx.repeat(2)) and torch.equal(idx_d.cpu(), idx)
+    out_d.fill_(-7)
+    N.check(unpack(lay=_args(shapes, ks, first=8)[1]), "arctopk_sparse_idx16_unpack")  # only a decode needs offsets[0] == 0
+    torch.cuda.synchronize()
+    assert torch.equal(out_d.cpu(), idx.repeat(2))
     assert _intact(ibuf, idx_d) and _intact(wbuf, wire_d) and _intact(obuf, out_d)
 
 
@@ -105,17 +127,26 @@ def _draws(name, nranks):
     return shapes, ks, all_idx, all_vals
 
 
-def _decode(shapes, ks, wires, vals, nranks, gE0, decay, shift=0):
-    """One arctopk_sparse_decode_idx16 between guards: (out, gE) on the CPU."""
+def _decode(shapes, ks, wires, vals, nranks, gE0, decay, shift=0, gap=0):
+    """One arctopk_sparse_decode_idx16 between guards, the payloads `gap` bytes apart, behind the calls it has to
+    refuse (which launch nothing): (out, gE) on the CPU."""
     numels, lay = _args(shapes, ks)
     n = sum(numels)
     obuf, out_d = _guarded(torch.full((n,), 5.0), shift)
     gbuf, gE_d = _guarded(gE0, shift) if gE0 is not None else (None, None)
-    wbuf, wire_d = _guarded(torch.cat(wires))
+    wbuf, wire_d = _guarded(torch.cat([torch.cat([w, torch.full((gap,), 0x5A, dtype=torch.uint8)]) for w in wires]))
     vbuf, vals_d = _guarded(torch.cat(vals))
-    N.check(N.lib().arctopk_sparse_decode_idx16(out_d.data_ptr(), *lay, sum(ks), wire_d.data_ptr(), wires[0].numel(),
-                                                vals_d.data_ptr(), N.DTYPE_CODE[vals[0].dtype], nranks, nranks,
-                                                N.ptr(gE_d), decay, _stream()), "arctopk_sparse_decode_idx16")
+
+    def decode(lay=lay, packed_len=sum(ks), wire=wire_d.data_ptr(), stride=wires[0].numel() + gap, nranks=nranks):
+        return N.lib().arctopk_sparse_decode_idx16(out_d.data_ptr(), *lay, packed_len, wire, stride, vals_d.data_ptr(),
+                                                   N.DTYPE_CODE[vals[0].dtype], nranks, len(wires), N.ptr(gE_d), decay,
+                                                   _stream())
+    refused = _bad_wire_args(sum(ks), wire_d.data_ptr(), wires[0].numel()) + [dict(lay=_args(shapes, ks, first=8)[1])]
+    for bad in refused:
+        assert decode(**bad) == N.EINVAL, bad
+    torch.cuda.synchronize()
+    assert bool((out_d == 5.0).all()) and (gE_d is None or torch.equal(gE_d.cpu(), gE0))
+    N.check(decode(), "arctopk_sparse_decode_idx16")
     torch.cuda.synchronize()
     assert _intact(obuf, out_d) and _intact(wbuf, wire_d) and _intact(vbuf, vals_d)
     assert gE_d is None or _intact(gbuf, gE_d)
@@ -133,7 +164,7 @@ def _want(shapes, ks, all_idx, all_vals, ws, gE0, decay):
 @pytest.mark.parametrize("decay", [None, 0.7])
 @pytest.mark.parametrize("vdtype", [F32, BF16])
 @pytest.mark.parametrize("nr", [1, 2, 3])
-@pytest.mark.parametrize("name", ["edge", "hand", "mix"])
+@pytest.mark.parametrize("name", ["edge", "hand", "mix", "batches"])
 def test_decode_phase(name, nr, vdtype, decay):
     shapes, ks, all_idx, all_vals = _draws(name, nr)
     numels = [S.numel_of(s) for s in shapes]
@@ -143,7 +174,8 @@ def test_decode_phase(name, nr, vdtype, decay):
     if decay is not None:
         gE0 = _grad(sum(numels), 9, 0.37)
         gE0[::5] = -0.0
-    out, gE = _decode(shapes, ks, wires, all_vals, nr, gE0, decay or 1.0, shift=int(name == "mix"))
+    out, gE = _decode(shapes, ks, wires, all_vals, nr, gE0, decay or 1.0, shift=int(name == "mix"),
+                      gap=16 * (name == "batches"))
     want_out, want_gE = _want(shapes, ks, all_idx, all_vals, nr, gE0, decay or 1.0)
     _same_bits(out, want_out, f"{name}/{nr}/{vdtype} out")
     if gE0 is not None:
