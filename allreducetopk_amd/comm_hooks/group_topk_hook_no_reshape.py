@@ -659,14 +659,25 @@ class GroupTopKState(HookState):
             raise ValueError("error_dtype=torch.float32 is built for use_error_feedback='ef14' only: "
                              "EF21 on a bfloat16 bucket keeps its residuals in bfloat16 unless "
                              "ef21_error_dtype=torch.float32 is set")
+        self._no_fp32_residual_rank()
         return True
+
+    def _no_fp32_residual_rank(self) -> None:
+        """ValueError at the sketch ranks of the matrix encode (r = 16, 32): the fp32-residual encode
+        keeps at most 8 sums per row, and the library refuses its calls there."""
+        if self.r > 8:
+            raise ValueError(f"error_dtype=torch.float32 and ef21_error_dtype=torch.float32 are built for "
+                             f"sketch ranks r <= 8, got r={self.r}: leave both None at r = 16 or 32")
 
     def _mixed21_residual(self, bucket_dtype, ef: int) -> bool:
         """Whether this call keeps both EF21 residuals in fp32 under a bf16 bucket.  ValueError for an
         ``ef21_error_dtype`` other than None / torch.float32; ignored for fp32 buckets, without
         error feedback and for EF14."""
-        return (self._fp32_residual_option("ef21_error_dtype")
-                and bucket_dtype == torch.bfloat16 and ef == N.EF21)
+        if not (self._fp32_residual_option("ef21_error_dtype")
+                and bucket_dtype == torch.bfloat16 and ef == N.EF21):
+            return False
+        self._no_fp32_residual_rank()
+        return True
 
     def residual_touched(self, b=None) -> None:
         """Tell the hook that bucket b's residual (None: every bucket's) was modified other than

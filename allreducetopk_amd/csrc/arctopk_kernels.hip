@@ -16,6 +16,7 @@
 #include <new>
 
 #include "common.h"
+#include "encode_mfma.h"
 #include "mselect.h"
 #include "mselect_dev.h"
 #include "vdraw.h"  // (fast contraction inside, for rocrand only)
@@ -3579,6 +3580,42 @@ int launch_encode_r(const arctopk_plan* p, const T* G, T* E, int ef, int err_in,
     return (int)hipGetLastError();
 }
 
+// r in {16, 32}: the plan's RAW tiles (and a riding pack's chunks) in the lean kernel -- the RAW
+// path does not depend on the rank --, its SKETCH tiles in the matrix encode (encode_mfma.hip), then
+// the partial-sketch sums; done: completed by the last of them.  No trailing step is carried and no
+// zero-rows kernel exists at these ranks (both gated on r == 4): err_in 2 runs as err_in 1.
+template <typename T>
+int launch_encode_mfma(const arctopk_plan* p, const T* G, T* E, int ef, int err_in, const T* V, T* sk,
+                       uint32_t* keys, hipStream_t st, PackRide<T> pr, hipEvent_t done) {
+    const int n_raw = p->n_enc_raw, n_mf = p->n_enc - p->n_enc_raw;
+    const hipEvent_t raw_done = n_mf == 0 && p->n_split == 0 ? done : nullptr;
+    if (n_raw > 0 || pr.n > 0) {
+        const dim3 grid(n_raw + pr.n), block(256);
+        const size_t lds = pr.n ? (size_t)kSmallTileRows * 4 : 0;
+        float* pb = p->d_part;
+        if (ef == ARCTOPK_EF_NONE)
+            launch_done(&k_encode_short<T, 1, ARCTOPK_EF_NONE, false>, grid, block, lds, st, raw_done, p->d_segs, p->d_enc, n_raw, G, E, V, sk, pb, keys, pr);
+        else if (ef == ARCTOPK_EF14 && err_in)
+            launch_done(&k_encode_short<T, 1, ARCTOPK_EF14, true>, grid, block, lds, st, raw_done, p->d_segs, p->d_enc, n_raw, G, E, V, sk, pb, keys, pr);
+        else if (ef == ARCTOPK_EF14)
+            launch_done(&k_encode_short<T, 1, ARCTOPK_EF14, false>, grid, block, lds, st, raw_done, p->d_segs, p->d_enc, n_raw, G, E, V, sk, pb, keys, pr);
+        else
+            launch_done(&k_encode_short<T, 1, ARCTOPK_EF21, true>, grid, block, lds, st, raw_done, p->d_segs, p->d_enc, n_raw, G, E, V, sk, pb, keys, pr);
+        const int e = (int)hipGetLastError();
+        if (e) return e;
+    }
+    const int e = encode_mfma(p, n_raw, n_mf, G, E, ef, err_in, V, sk, keys, st, p->n_split == 0 ? done : nullptr);
+    if (e) return e;
+    if (p->n_split == 0) {
+        if (done && n_mf == 0 && !(n_raw > 0 || pr.n > 0)) return (int)hipEventRecord(done, st);
+        return 0;
+    }
+    const int gx = (int)std::min<int64_t>(256, (p->split_rows_max * p->r + 255) / 256);
+    launch_done(&k_sketch_combine<T>, dim3(gx, p->n_split), dim3(256), 0, st, done, (const SegDev*)p->d_segs,
+                (const int32_t*)p->d_split, (int)p->r, (const float*)p->d_part, sk);
+    return (int)hipGetLastError();
+}
+
 template <typename T>
 int launch_encode(const arctopk_plan* p, const void* grad, void* err, int ef, int err_in, const void* V,
                   void* sketch, uint32_t* keys, hipStream_t st, PackRide<T> pr = PackRide<T>{},
@@ -3591,6 +3628,10 @@ int launch_encode(const arctopk_plan* p, const void* grad, void* err, int ef, in
     // X = G + E itself, with this call's err_in (host bookkeeping of the plan, like x_*)
     const_cast<arctopk_plan*>(p)->dense_err_in = err_in;
     if (ef != ARCTOPK_EF14) zr_clear(p);  // a step in another EF mode: the residual is not EF14's
+    if (rank_mfma(p->r)) {
+        if (er.n > 0) return ARCTOPK_EINVAL;  // (a trailing step is carried at r = 4 only)
+        return launch_encode_mfma<T>(p, G, E, ef, err_in, Vt, sk, keys, st, pr, done);
+    }
     switch (p->r) {
         case 1: return launch_encode_r<T, 1>(p, G, E, ef, err_in, Vt, sk, keys, st, pr, done, er, er_lds, er_short);
         case 2: return launch_encode_r<T, 2>(p, G, E, ef, err_in, Vt, sk, keys, st, pr, done, er, er_lds, er_short);

@@ -95,7 +95,8 @@
 
 namespace arctopk {
 
-constexpr int kMaxR = 8;           // sketch rank supported by the kernels
+constexpr int kMaxR = 8;           // largest sketch rank of the VALU encode (k_encode); ranks 16 and 32 run the
+                                   // matrix encode (encode_mfma.h: kMaxRank, rank_ok)
 constexpr int kTileRows = 256;     // row granule of a small-m encode tile (thread per row)
 #ifndef ARCTOPK_SMALL_TILE_BYTES
 #define ARCTOPK_SMALL_TILE_BYTES 16384  // 16 KiB: ResNet-18 DDP buckets 228 -> 234 GB/s, large buckets unchanged
@@ -314,7 +315,8 @@ constexpr bool kEncNtStore = true;
 constexpr int kSmallTileRows = 1024;  // rows of a small-m pack/decode chunk (LDS slot table)
 
 // encode tile modes
-enum : int32_t { ENC_ROW_VEC = 0, ENC_ROW_SCALAR = 1, ENC_TILE = 2, ENC_RAW = 3 };
+enum : int32_t { ENC_ROW_VEC = 0, ENC_ROW_SCALAR = 1, ENC_TILE = 2, ENC_RAW = 3,
+                 ENC_MFMA = 4 };  // r in {16, 32}: every SKETCH tile (encode_mfma.hip)
 // pack / decode chunk mode of a DENSE segment (every element selected, no row list or slot map)
 constexpr int32_t kChunkDense = 4;
 
@@ -384,7 +386,8 @@ struct arctopk_plan {
     int n_enc_e;
     int enc_lds_bytes;            // dynamic LDS of the encode launch
     int enc_short;                // no wave-per-row tile in the tables: k_encode_short
-    int enc_mode_tiles[4];        // tiles of d_enc per mode (index ENC_*; arctopk_diag_encode_tiles)
+    int enc_mode_tiles[5];        // tiles of d_enc per mode (index ENC_*; arctopk_diag_encode_tiles)
+    int n_enc_raw;                // r in {16, 32}: d_enc holds this many ENC_RAW tiles, then the ENC_MFMA tiles
     int n_keyed;                  // `keyed` segments (SegDev)
     int dense_err_in;             // err_in of the plan's last encode: a DENSE segment has no encode
                                   // tile, so EF14's X = G + E (err_in) or G is formed by its pack

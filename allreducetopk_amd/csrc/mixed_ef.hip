@@ -536,6 +536,7 @@ int mixed_table(const arctopk_plan* p, MxTab** out) {
 int mixed_begin(const arctopk_plan* p, uintptr_t misaligned, int MxTab::*count, MxTab** out) {
     *out = nullptr;
     if (p->dtype != ARCTOPK_BF16 || misaligned) return ARCTOPK_EINVAL;
+    if (p->r > kMaxR) return ARCTOPK_EINVAL;  // (the encode here keeps kMaxR sums per row: no rank 16 or 32)
     MxTab* t = nullptr;
     const int st = mixed_table(p, &t);
     if (st == 0 && t->*count > 0) *out = t;

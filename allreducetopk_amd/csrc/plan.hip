@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "common.h"
+#include "encode_mfma.h"
 #include "mselect.h"
 
 using namespace arctopk;
@@ -94,7 +95,7 @@ extern "C" int arctopk_plan_create_ex(const int64_t* dims, const int32_t* ndims,
                                       int32_t flags, arctopk_plan** out) {
     if (!dims || !ndims || !out || ntensors < 1) return ARCTOPK_EINVAL;
     if (flags & ~(ARCTOPK_PLAN_DENSE_1D | ARCTOPK_PLAN_RESTART_DRAWS)) return ARCTOPK_EINVAL;
-    if (r < 1 || r > kMaxR) return ARCTOPK_EINVAL;
+    if (!rank_ok(r)) return ARCTOPK_EINVAL;
     if (!(compress_ratio > 0.0) || compress_ratio > 1.0) return ARCTOPK_EINVAL;
     if (dtype != ARCTOPK_F32 && dtype != ARCTOPK_BF16) return ARCTOPK_EDTYPE;
     *out = nullptr;
@@ -141,6 +142,21 @@ extern "C" int arctopk_plan_create_ex(const int64_t* dims, const int32_t* ndims,
         65536, std::max<int64_t>(ARCTOPK_ENC_MIN_TILE, row_work / (int64_t)ARCTOPK_ENC_TARGET_BLOCKS_E));
     std::vector<EncTile> enc_e;
     bool any_e = false;
+    // r in {16, 32}: the matrix encode's tiles (encode_mfma.h), kept after the RAW tiles in `enc`.
+    // A block takes whole row tiles of r rows: one while the bucket has fewer than the block target
+    // of them, more (up to kMfTileRows rows, one staging of V^T for all) in larger buckets.  A
+    // bucket of fewer than kMfFillBlocks row tiles (one [2048, 2048] tensor: 64 at r = 32) splits
+    // wide rows into column parts of whole K-slabs, so its blocks still cover the CUs.
+    std::vector<EncTile> enc_mf;
+    int64_t mf_row_tiles = 0;
+    if (rank_mfma(r))
+        for (const arctopk_segment& s : segs)
+            if (s.kind == ARCTOPK_SEG_SKETCH) mf_row_tiles += (s.n + r - 1) / r;
+    const int64_t mf_tile_rows =
+        r * std::min<int64_t>(kMfTileRows / r, std::max<int64_t>(1, mf_row_tiles / target));
+    const int64_t mf_slab = kMfSlabBytes / (dtype == ARCTOPK_BF16 ? 2 : 4);  // columns per K-slab
+    const int64_t mf_want_parts =
+        mf_row_tiles > 0 && mf_row_tiles < kMfFillBlocks ? (kMfFillBlocks + mf_row_tiles - 1) / mf_row_tiles : 1;
     // chunk sizes (build-time A/B switches, common.h): short rows (m < 256) and the m <= 2
     // streams get smaller chunks, more blocks in flight (ResNet-50 1x1 mix, 2048-element
     // stream pack chunks: 346 -> 356 GB/s; 4096-element decode chunks: +3 %)
@@ -193,6 +209,22 @@ extern "C" int arctopk_plan_create_ex(const int64_t* dims, const int32_t* ndims,
             for (int64_t e = 0; e < s.n; e += per)
                 for (std::vector<EncTile>* dst : {&enc, &enc_e})
                     dst->push_back(EncTile{(int32_t)i, ENC_RAW, e, std::min(per, s.n - e), 0, 1, -1, 1});
+        } else if (rank_mfma(r)) {
+            const int64_t slabs = (s.m + mf_slab - 1) / mf_slab;
+            const int64_t clen = (slabs + std::min(mf_want_parts, slabs) - 1) / std::min(mf_want_parts, slabs) * mf_slab;
+            const int nparts = (int)((s.m + clen - 1) / clen);
+            if (nparts > 1) {
+                g.nparts = nparts;
+                g.part_off = part_len;
+                part_len += (int64_t)nparts * s.n * r;
+                split_ids.push_back((int32_t)i);
+                split_rows_max = std::max<int64_t>(split_rows_max, s.n);
+            }
+            for (int part = 0; part < nparts; ++part)
+                for (int64_t row = 0; row < s.n; row += mf_tile_rows)
+                    enc_mf.push_back(EncTile{(int32_t)i, ENC_MFMA, row, std::min<int64_t>(mf_tile_rows, s.n - row),
+                                             (int32_t)(part * clen), (int32_t)std::min<int64_t>(clen, s.m - part * clen),
+                                             nparts > 1 ? part : -1, 1});
         } else if (s.m < kSmallM && (kTileRows * s.m + s.m * r) * 4 <= 65536) {
             // rows per tile: ~kSmallTileBytes of the tensor (multiples of 256 rows), so the
             // smallest m (1x1 convs, m = 2) does not run thousands of 2 KiB blocks
@@ -299,6 +331,8 @@ extern "C" int arctopk_plan_create_ex(const int64_t* dims, const int32_t* ndims,
     const int32_t n_dec_sparse = (int32_t)dec.size();
     for (int32_t& b : ddec_begin) b += n_dec_sparse;
     dec.insert(dec.end(), dec_dense.begin(), dec_dense.end());
+    const int n_enc_raw = rank_mfma(r) ? (int)enc.size() : 0;  // (the RAW tiles: the lean kernel runs them)
+    enc.insert(enc.end(), enc_mf.begin(), enc_mf.end());
 
     hipError_t e = hipSetDevice(device);
     if (e != hipSuccess) return (int)e;
@@ -316,6 +350,7 @@ extern "C" int arctopk_plan_create_ex(const int64_t* dims, const int32_t* ndims,
     p->h_segs = new arctopk_segment[segs.size()];
     std::copy(segs.begin(), segs.end(), p->h_segs);
     p->n_enc = (int)enc.size();
+    p->n_enc_raw = n_enc_raw;
     p->n_enc_e = dtype == ARCTOPK_F32 && any_e ? (int)enc_e.size() : 0;
     p->n_pack = (int)pack.size();
     p->n_dec = (int)dec.size();
@@ -526,7 +561,7 @@ extern "C" int arctopk_plan_describe_ex(const int64_t* dims, const int32_t* ndim
                                         arctopk_segment* segs_out, arctopk_plan_info* info) {
     if (!dims || !ndims || !info || ntensors < 1) return ARCTOPK_EINVAL;
     if (flags & ~(ARCTOPK_PLAN_DENSE_1D | ARCTOPK_PLAN_RESTART_DRAWS)) return ARCTOPK_EINVAL;
-    if (r < 1 || r > kMaxR) return ARCTOPK_EINVAL;
+    if (!rank_ok(r)) return ARCTOPK_EINVAL;
     if (!(compress_ratio > 0.0) || compress_ratio > 1.0) return ARCTOPK_EINVAL;
     std::vector<arctopk_segment> segs;
     std::memset(info, 0, sizeof(*info));

@@ -115,6 +115,10 @@ typedef struct {
  * k follow the reference: 1-D -> RAW; 2-D -> [shape0, shape1]; ND -> [d/m, m]
  * with m = 2*shape[-1]^2 (group_topk_hook_no_reshape.py:16-102, cal_k :173-187).
  * Replaces: the per-call Python loop over bucket.gradients() (:111-129, :259).
+ * r: the sketch rank, one of 1..8 (the VALU encode), 16 or 32 (the matrix-instruction encode);
+ * any other value is ARCTOPK_EINVAL, here and in arctopk_plan_describe.  At r = 16 and 32 the
+ * fp32-residual phases (arctopk_encode_mixed and its kin) return ARCTOPK_EINVAL, and the
+ * zero-rows encode and the carried trailing step (both r = 4 only) are not taken.
  */
 int arctopk_plan_create(const int64_t* dims, const int32_t* ndims, int32_t ntensors, int32_t r,
                         double compress_ratio, int32_t dtype, int32_t device, arctopk_plan** out);
