@@ -611,6 +611,31 @@ class GroupTopKState(HookState):
             raise ValueError(f"ARCTOPK_WIRE_EXCHANGE must be 'step' (or unset), got {env!r}")
         self.wire_exchange = "step" if env == "step" else "inline"
         self.wire16_step_calls = 0  # ... those of them that went through the exchange step
+        # Operand dtype of the sketch projection at r = 16 / 32 (not in the
+        # reference): None multiplies an fp32 bucket's X and V as fp32; torch.bfloat16 rounds both to
+        # bf16 on their way into the matrix units (an eighth of the matrix instructions).  Only the
+        # sketch -- the ranking of rows -- sees the rounding: residuals, packed values and the wire
+        # do not.  Ignored for bf16 buckets, whose operands are bf16 already; ValueError at r <= 8.
+        # Set once per plan (arctopk_plan_set_sketch_operands); every path of the call takes it.
+        # Environment default: ARCTOPK_SKETCH_OPERAND_DTYPE=bf16.
+        env = os.environ.get("ARCTOPK_SKETCH_OPERAND_DTYPE", "")
+        if env not in ("", "bf16"):
+            raise ValueError(f"ARCTOPK_SKETCH_OPERAND_DTYPE must be 'bf16' (or unset), got {env!r}")
+        self.sketch_operand_dtype = torch.bfloat16 if env == "bf16" else None
+
+    def _sketch_op16(self, bucket_dtype) -> bool:
+        """Whether this bucket's plan multiplies bf16 operands in its fp32 sketch projection.
+        ValueError for a ``sketch_operand_dtype`` other than None / torch.bfloat16, and for a sketch
+        rank other than 16 / 32 with it (r <= 8 has no matrix encode); ignored for bf16 buckets."""
+        sd = self.sketch_operand_dtype
+        if sd is None:
+            return False
+        if sd is not torch.bfloat16:
+            raise ValueError(f"sketch_operand_dtype must be None or torch.bfloat16, got {sd!r}")
+        if self.r not in (16, 32):
+            raise ValueError(f"sketch_operand_dtype=torch.bfloat16 is built for sketch ranks r = 16 and 32, "
+                             f"got r={self.r}: leave it None")
+        return bucket_dtype == torch.float32
 
     def _wire16_step(self, wire16: bool) -> bool:
         """Whether a bf16-wire call (`wire16`: what _wire16 returned) goes through the exchange step.
@@ -807,6 +832,7 @@ class GroupTopKState(HookState):
         # under either setting
         out["wire_dtype"] = "bf16" if self.wire_dtype is torch.bfloat16 else None
         out["wire_exchange"] = self.wire_exchange  # (where the call runs: the residuals do not depend on it)
+        out["sketch_operand_dtype"] = "bf16" if self.sketch_operand_dtype is torch.bfloat16 else None
         return out
 
     def load_state_dict(self, sd: dict, device=None) -> None:
@@ -888,14 +914,15 @@ class GroupTopKState(HookState):
         # fast path: the bucket's flat buffer is the one this plan was built for (DDP keeps a
         # bucket's buffer across iterations; its one-time rebuild falls in the check window)
         ratio, flags = self._plan_ratio(), self._plan_flags()
-        ident = (buf.data_ptr(), buf.numel(), buf.dtype, self.r, ratio, flags)
+        op16 = self._sketch_op16(buf.dtype)  # (part of the plan's identity: a changed option makes a new plan)
+        ident = (buf.data_ptr(), buf.numel(), buf.dtype, self.r, ratio, flags, op16)
         hit = self._plans.get(bucket.index())
         if (hit is not None and hit[2] == ident
                 and self.iter >= self._first_compressed_iter + self.layout_check_iters):
             return hit[1]
         grads = bucket.gradients()
         shapes = [tuple(g.shape) for g in grads]
-        key = (tuple(shapes), buf.dtype, buf.device, self.r, ratio, flags)
+        key = (tuple(shapes), buf.dtype, buf.device, self.r, ratio, flags, op16)
         if hit is not None and hit[0] == key:
             self._plans[bucket.index()] = (key, hit[1], ident)
             return hit[1]
@@ -909,6 +936,8 @@ class GroupTopKState(HookState):
                 if hit[1].packed16 is not None:
                     c.unregister(hit[1].packed16)
         plan = BucketPlan(shapes, self.r, ratio, buf.dtype, buf.device, flags)
+        if op16:  # (before the plan's first encode and before its exchange groups are made)
+            N.check(_LIB[0].arctopk_plan_set_sketch_operands(plan.handle, N.BF16), "arctopk_plan_set_sketch_operands")
         self._plans[bucket.index()] = (key, plan, ident)
         return plan
 
@@ -1447,6 +1476,7 @@ def group_topk_hook(state: GroupTopKState, bucket: dist.GradBucket
     # an fp32 bucket whose packed values travel as bf16 (state.wire_dtype)
     wire16 = state._wire16(input_tensor.dtype)
     w16step = state._wire16_step(wire16)  # ... through the exchange step (state.wire_exchange)
+    state._sketch_op16(input_tensor.dtype)  # (state.sketch_operand_dtype: raises here; applied by _plan_for)
     if ef == N.EF14:
         if b not in state.error_dict:
             logger.info("A zero tensor of length %s that represents local error is created.", total)

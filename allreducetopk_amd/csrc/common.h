@@ -485,6 +485,8 @@ struct arctopk_plan {
                                         //   (wire16.hip), built by the plan's first call there
     void* b_packed16;                   // bound by arctopk_plan_bind_wire16: the plan's exchange steps
                                         //   send their packed values through it as bf16 (NULL: b_packed)
+    int sketch_op16;                    // set by arctopk_plan_set_sketch_operands (fp32 plan, r 16 / 32): the
+                                        //   matrix encode rounds X and V to bf16 operands (encode_mfma.hip)
     int x_w16;                          // the deferred step is such a one (beside x_ef / x_ws): its
                                         //   decode is arctopk_decode_wire16 of b_packed16
     int64_t w16_scatters;               // steps whose decode was the zero-ahead scatter (diagnostics)

@@ -18,6 +18,13 @@
 // are in flight in registers while the current one is multiplied.  At the tile's end the waves'
 // partial accumulators are summed through LDS in wave order and stored (sketch in the bucket
 // dtype, rounded once; fp32 partials of a column part; or the row's energy key in keys mode).
+//
+// bf16 operands of an fp32 bucket (arctopk_plan_set_sketch_operands; DESIGN.md 4k, "bf16 operands"):
+// G, E and V stay fp32 in memory and the slab stays 256 columns, so the plan's tiles, the X prefetch
+// and the E store are the fp32 kernel's; X (after the fp32 EF rule and the E store) and V are rounded
+// with cvt_pk_bf16 on their way into LDS, whose rows then hold 256 bf16 (528 B with the padding, half
+// the bytes) in the bf16 kernel's layout, and the walk issues the bf16 MFMAs: one per k-group of
+// 8 H columns where the fp32 operands take four.
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
@@ -31,9 +38,7 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 typedef float v16f __attribute__((ext_vector_type(16)));
 typedef __bf16 bf8_t __attribute__((ext_vector_type(8)));
 
-constexpr int kSlabUnits = kMfSlabBytes / 16;  // 16-B units per row per slab
-constexpr int kRowUnits = kMfRowBytes / 16;    // LDS row stride in units
-constexpr int kRowWords = kMfRowBytes / 4;
+constexpr int kSlabUnits = kMfSlabBytes / 16;  // 16-B units of G (and of E) per row per slab
 
 template <int R> struct Acc;
 template <> struct Acc<32> { typedef v16f type; static constexpr int N = 16; };
@@ -94,8 +99,15 @@ __device__ __forceinline__ uint32_t row_key(const float* __restrict__ p, int R) 
     return u & 0x7FFFFFFFu ? u : 0u;
 }
 
-template <typename T, int R, int EF, bool ERR_IN>
-__global__ void __launch_bounds__(256) k_encode_mfma(const SegDev* __restrict__ segs,
+// T: the bucket's element type in memory; O: the operands' type in LDS and in the MFMA -- T itself,
+// or bf16_t under an fp32 bucket (arctopk_plan_set_sketch_operands): X and V are then rounded
+// on their way into LDS, E and the sums stay fp32.  At r = 32 that variant is built for three waves
+// per SIMD: its 33,792 B of LDS let three blocks share a CU, which the compiler's 140 + 32 registers
+// miss by four (168 with 4 VGPRs spilled under EF14 / EF21); measured 216 -> 177 us on the headline
+// bucket.  0: every other instantiation is left to the compiler, as before.
+template <typename T, typename O, int R, int EF, bool ERR_IN>
+__global__ void __launch_bounds__(256)
+__attribute__((amdgpu_waves_per_eu(sizeof(O) != sizeof(T) && R == 32 ? 3 : 0))) k_encode_mfma(const SegDev* __restrict__ segs,
                                                      const EncTile* __restrict__ tiles,
                                                      const T* __restrict__ G, T* __restrict__ E,
                                                      const T* __restrict__ V, T* __restrict__ sketch,
@@ -104,10 +116,17 @@ __global__ void __launch_bounds__(256) k_encode_mfma(const SegDev* __restrict__ 
     constexpr int TR = R;                 // rows of a row tile (the MFMA's N)
     constexpr int H = 64 / R;             // lane groups: 16-B units of a k-group
     constexpr int NT = kMfTileRows / TR;  // row tiles of a block at most
-    constexpr int EPU = 16 / (int)sizeof(T);  // elements per unit
+    constexpr bool OPB = sizeof(O) != sizeof(T);  // bf16 operands of an fp32 bucket
+    constexpr int EPU = 16 / (int)sizeof(T);  // elements per unit of G / E / V
+    constexpr int LPU = 16 / (int)sizeof(O);  // ... and per unit of an LDS row
+    constexpr int UR = LPU / EPU;             // units of G that make one LDS unit (1; OPB: 2)
     constexpr int SLAB = kSlabUnits * EPU;    // columns per slab
+    constexpr int kRowUnits = SLAB / LPU + 1;  // LDS row stride in units: the slab and one unit of padding
+    constexpr int kRowWords = kRowUnits * 4;
     constexpr int XU = TR / 4;                // X units per thread per row tile
-    constexpr int VU = sizeof(T) == 4 ? R / 4 : R / 8;  // V work items per thread per slab
+    constexpr int VU = sizeof(O) == 4 ? R / 4 : R / 8;  // V work items per thread per slab
+    static_assert(2 * R * kRowUnits * 16 <= 2 * R * kMfRowBytes && 4 * R * 4 <= kRowUnits * 16,
+                  "V^T and X fit the plan's LDS bound; the waves' partial sums fit the X tile");
     constexpr bool LOAD_E = (EF == ARCTOPK_EF21) || (EF == ARCTOPK_EF14 && ERR_IN);
     constexpr bool WRITE_E = EF == ARCTOPK_EF14;
     typedef typename Acc<R>::type acc_t;
@@ -135,14 +154,15 @@ __global__ void __launch_bounds__(256) k_encode_mfma(const SegDev* __restrict__ 
 #pragma unroll
         for (int q = 0; q < Acc<R>::N; ++q) acc[i][q] = 0.f;
 
-    // columns, units and (whole k-groups of) units of a slab
+    // columns and LDS units (whole k-groups) of a slab
     auto slab_cols = [&](int sl) { return min(SLAB, cl - sl * SLAB); };
-    auto slab_ku = [&](int sl) { return ((slab_cols(sl) + EPU - 1) / EPU + H - 1) / H * H; };
+    auto slab_ku = [&](int sl) { return ((slab_cols(sl) + LPU - 1) / LPU + H - 1) / H * H; };
 
     // ---- X tile (slab sl, row tile nt): thread e = tid + 256 i takes unit e % ku of tile row e / ku
+    // (units of G; OPB: a wave's lanes then write consecutive 8-B halves of LDS units, 512 B in a row)
     u4_t gx[XU], ex[XU];
     auto issue_x = [&](int sl, int nt) {
-        const int cols = slab_cols(sl), ku = slab_ku(sl);
+        const int cols = slab_cols(sl), ku = slab_ku(sl) * UR;
         const int units = cols / EPU;  // (vector path: cols is a multiple of EPU)
         const int64_t r0 = t.row0 + (int64_t)nt * TR;
 #pragma unroll
@@ -159,7 +179,7 @@ __global__ void __launch_bounds__(256) k_encode_mfma(const SegDev* __restrict__ 
         }
     };
     auto stash_x = [&](int sl, int nt) {
-        const int cols = slab_cols(sl), ku = slab_ku(sl);
+        const int cols = slab_cols(sl), ku = slab_ku(sl) * UR;
         const int units = cols / EPU;
         const int64_t r0 = t.row0 + (int64_t)nt * TR;
 #pragma unroll
@@ -175,14 +195,19 @@ __global__ void __launch_bounds__(256) k_encode_mfma(const SegDev* __restrict__ 
                     else *ep = x;
                 }
             }
-            xt[rr * kRowUnits + u] = x;
+            if constexpr (OPB)  // (after the fp32 E store: only the operand is rounded)
+                reinterpret_cast<u2_t*>(xt + rr * kRowUnits)[u] =
+                    u2_t{cvt_pk_bf16(__uint_as_float(x.x), __uint_as_float(x.y)),
+                         cvt_pk_bf16(__uint_as_float(x.z), __uint_as_float(x.w))};
+            else
+                xt[rr * kRowUnits + u] = x;
         }
     };
     // the same tile element by element (odd offsets, m no multiple of the unit): no prefetch
     auto stash_x_scalar = [&](int sl, int nt) {
-        const int cols = slab_cols(sl), kuc = slab_ku(sl) * EPU;
+        const int cols = slab_cols(sl), kuc = slab_ku(sl) * LPU;
         const int64_t r0 = t.row0 + (int64_t)nt * TR;
-        T* const xl = reinterpret_cast<T*>(xt);
+        O* const xl = reinterpret_cast<O*>(xt);
         for (int e = tid; e < TR * kuc; e += 256) {
             const int rr = e / kuc, cc = e - rr * kuc;
             float x = 0.f;
@@ -193,13 +218,14 @@ __global__ void __launch_bounds__(256) k_encode_mfma(const SegDev* __restrict__ 
                 else if constexpr (EF == ARCTOPK_EF21) x = rnd<T>(x - ld1<T, true>(Es + at));
                 if constexpr (WRITE_E) st1<T, true>(Es + at, x);
             }
-            xl[rr * (kRowUnits * EPU) + cc] = from_f<T>(x);
+            xl[rr * (kRowUnits * LPU) + cc] = from_f<O>(x);
         }
     };
 
     // ---- V^T slab: V[c0 + sl SLAB + col][0..R) read in 16-B units (L2-resident), transposed into LDS.
-    // fp32: item = (col, 4 ranks); bf16: item = (column pair, 8 ranks), the pair packed into one word
-    u4_t va[VU], vb[sizeof(T) == 4 ? 1 : VU];
+    // fp32: item = (col, 4 ranks); bf16: item = (column pair, 8 ranks), the pair packed into one word;
+    // OPB: item = (column pair, 4 fp32 ranks), each rank's pair rounded into one word
+    u4_t va[VU], vb[sizeof(O) == 4 ? 1 : VU];
     auto issue_v = [&](int sl) {
         const int cols = slab_cols(sl);
         const T* vp = Vs + (int64_t)(c0 + sl * SLAB) * R;
@@ -207,34 +233,41 @@ __global__ void __launch_bounds__(256) k_encode_mfma(const SegDev* __restrict__ 
         for (int i = 0; i < VU; ++i) {
             const int idx = tid + 256 * i;
             va[i] = u4_t{0u, 0u, 0u, 0u};
-            if constexpr (sizeof(T) == 4) {
+            if constexpr (sizeof(O) == 4) {
                 const int col = idx / (R / 4), jq = idx % (R / 4);
                 if (col < cols) va[i] = ld16raw<T, false>(vp, col * (R / 4) + jq);
             } else {
-                const int cp = idx / (R / 8), jg = idx % (R / 8);
+                const int cp = idx / (R / EPU), jg = idx % (R / EPU);
                 vb[i] = u4_t{0u, 0u, 0u, 0u};
-                if (2 * cp < cols) va[i] = ld16raw<T, false>(vp, 2 * cp * (R / 8) + jg);
-                if (2 * cp + 1 < cols) vb[i] = ld16raw<T, false>(vp, (2 * cp + 1) * (R / 8) + jg);
+                if (2 * cp < cols) va[i] = ld16raw<T, false>(vp, 2 * cp * (R / EPU) + jg);
+                if (2 * cp + 1 < cols) vb[i] = ld16raw<T, false>(vp, (2 * cp + 1) * (R / EPU) + jg);
             }
         }
     };
     auto stash_v = [&](int sl) {
-        const int kuc = slab_ku(sl) * EPU;
+        const int kuc = slab_ku(sl) * LPU;
         uint32_t* const vw = reinterpret_cast<uint32_t*>(vt);
 #pragma unroll
         for (int i = 0; i < VU; ++i) {
             const int idx = tid + 256 * i;
             const uint32_t aw[4] = {va[i].x, va[i].y, va[i].z, va[i].w};
-            if constexpr (sizeof(T) == 4) {
+            if constexpr (sizeof(O) == 4) {
                 const int col = idx / (R / 4), jq = idx % (R / 4);
                 if (col < kuc) {
 #pragma unroll
                     for (int q = 0; q < 4; ++q) vw[(jq * 4 + q) * kRowWords + col] = aw[q];
                 }
             } else {
-                const int cp = idx / (R / 8), jg = idx % (R / 8);
+                const int cp = idx / (R / EPU), jg = idx % (R / EPU);
                 const uint32_t bw[4] = {vb[i].x, vb[i].y, vb[i].z, vb[i].w};
-                if (2 * cp < kuc) {
+                if constexpr (OPB) {
+                    if (2 * cp < kuc) {
+#pragma unroll
+                        for (int q = 0; q < 4; ++q)
+                            vw[(jg * 4 + q) * kRowWords + cp] =
+                                cvt_pk_bf16(__uint_as_float(aw[q]), __uint_as_float(bw[q]));
+                    }
+                } else if (2 * cp < kuc) {
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         vw[(jg * 8 + 2 * q) * kRowWords + cp] = (aw[q] & 0xFFFFu) | (bw[q] << 16);
@@ -266,7 +299,7 @@ __global__ void __launch_bounds__(256) k_encode_mfma(const SegDev* __restrict__ 
                 __syncthreads();
                 for (int kg = wave; kg < ngroups; kg += 4) {
                     const int u = kg * H + lh;
-                    mfma_unit<T, R>(acc[nt], vt[ln * kRowUnits + u], xt[ln * kRowUnits + u]);
+                    mfma_unit<O, R>(acc[nt], vt[ln * kRowUnits + u], xt[ln * kRowUnits + u]);
                 }
             }
         }
@@ -313,31 +346,31 @@ int launch(K k, int ntiles, size_t lds, hipStream_t st, hipEvent_t done, Args...
     return (int)hipGetLastError();
 }
 
-template <typename T, int R, int EF, bool ERR_IN>
+template <typename T, typename O, int R, int EF, bool ERR_IN>
 int launch_k(const arctopk_plan* p, int tile0, int ntiles, const T* G, T* E, const T* V, T* sk, uint32_t* keys,
              hipStream_t st, hipEvent_t done) {
-    constexpr size_t lds = 2 * (size_t)R * kMfRowBytes;
+    constexpr size_t lds = 2 * (size_t)R * (kMfSlabBytes / (sizeof(T) / sizeof(O)) + 16);  // V^T and X rows of O
     if constexpr (lds > 48 * 1024) {  // (on every launch: the attribute is per device, the call is cheap)
         const hipError_t ok =
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_encode_mfma<T, R, EF, ERR_IN>),
+            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_encode_mfma<T, O, R, EF, ERR_IN>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (ok != hipSuccess) return (int)ok;
     }
-    return launch(&k_encode_mfma<T, R, EF, ERR_IN>, ntiles, lds, st, done, (const SegDev*)p->d_segs,
+    return launch(&k_encode_mfma<T, O, R, EF, ERR_IN>, ntiles, lds, st, done, (const SegDev*)p->d_segs,
                   (const EncTile*)(p->d_enc + tile0), G, E, V, sk, p->d_part, keys);
 }
 
-template <typename T, int R>
+template <typename T, typename O, int R>
 int launch_r(const arctopk_plan* p, int tile0, int ntiles, const void* grad, void* err, int ef, int err_in,
              const void* V, void* sketch, uint32_t* keys, hipStream_t st, hipEvent_t done) {
     const T* G = static_cast<const T*>(grad);
     T* E = static_cast<T*>(err);
     const T* Vt = static_cast<const T*>(V);
     T* sk = static_cast<T*>(sketch);
-    if (ef == ARCTOPK_EF_NONE) return launch_k<T, R, ARCTOPK_EF_NONE, false>(p, tile0, ntiles, G, E, Vt, sk, keys, st, done);
-    if (ef == ARCTOPK_EF14 && err_in) return launch_k<T, R, ARCTOPK_EF14, true>(p, tile0, ntiles, G, E, Vt, sk, keys, st, done);
-    if (ef == ARCTOPK_EF14) return launch_k<T, R, ARCTOPK_EF14, false>(p, tile0, ntiles, G, E, Vt, sk, keys, st, done);
-    if (ef == ARCTOPK_EF21) return launch_k<T, R, ARCTOPK_EF21, true>(p, tile0, ntiles, G, E, Vt, sk, keys, st, done);
+    if (ef == ARCTOPK_EF_NONE) return launch_k<T, O, R, ARCTOPK_EF_NONE, false>(p, tile0, ntiles, G, E, Vt, sk, keys, st, done);
+    if (ef == ARCTOPK_EF14 && err_in) return launch_k<T, O, R, ARCTOPK_EF14, true>(p, tile0, ntiles, G, E, Vt, sk, keys, st, done);
+    if (ef == ARCTOPK_EF14) return launch_k<T, O, R, ARCTOPK_EF14, false>(p, tile0, ntiles, G, E, Vt, sk, keys, st, done);
+    if (ef == ARCTOPK_EF21) return launch_k<T, O, R, ARCTOPK_EF21, true>(p, tile0, ntiles, G, E, Vt, sk, keys, st, done);
     return ARCTOPK_EINVAL;
 }
 
@@ -348,12 +381,15 @@ int encode_mfma(const arctopk_plan* p, int tile0, int ntiles, const void* grad, 
                 const void* V, void* sketch, uint32_t* keys, hipStream_t st, hipEvent_t done) {
     if (ntiles <= 0) return 0;
     const bool bf = p->dtype == ARCTOPK_BF16;
+    const bool opb = !bf && p->sketch_op16;  // arctopk_plan_set_sketch_operands(ARCTOPK_BF16)
     if (p->r == 32)
-        return bf ? launch_r<bf16_t, 32>(p, tile0, ntiles, grad, err, ef, err_in, V, sketch, keys, st, done)
-                  : launch_r<float, 32>(p, tile0, ntiles, grad, err, ef, err_in, V, sketch, keys, st, done);
+        return bf    ? launch_r<bf16_t, bf16_t, 32>(p, tile0, ntiles, grad, err, ef, err_in, V, sketch, keys, st, done)
+               : opb ? launch_r<float, bf16_t, 32>(p, tile0, ntiles, grad, err, ef, err_in, V, sketch, keys, st, done)
+                     : launch_r<float, float, 32>(p, tile0, ntiles, grad, err, ef, err_in, V, sketch, keys, st, done);
     if (p->r == 16)
-        return bf ? launch_r<bf16_t, 16>(p, tile0, ntiles, grad, err, ef, err_in, V, sketch, keys, st, done)
-                  : launch_r<float, 16>(p, tile0, ntiles, grad, err, ef, err_in, V, sketch, keys, st, done);
+        return bf    ? launch_r<bf16_t, bf16_t, 16>(p, tile0, ntiles, grad, err, ef, err_in, V, sketch, keys, st, done)
+               : opb ? launch_r<float, bf16_t, 16>(p, tile0, ntiles, grad, err, ef, err_in, V, sketch, keys, st, done)
+                     : launch_r<float, float, 16>(p, tile0, ntiles, grad, err, ef, err_in, V, sketch, keys, st, done);
     return ARCTOPK_EINVAL;
 }
 }  // namespace arctopk

@@ -546,7 +546,16 @@ extern "C" int arctopk_plan_group(const arctopk_plan* parent, int32_t seg_begin,
     c->n_vdraw = (int)mine.size();
     c->n_vchunk = (int)vc.size();
     c->vdraw_advance = parent->vdraw_advance;  // (the bucket's: reseeds use the parent's)
+    c->sketch_op16 = parent->sketch_op16;      // (as set when the group is made)
     *out = c;
+    return 0;
+}
+
+extern "C" int arctopk_plan_set_sketch_operands(arctopk_plan* p, int32_t dtype) {
+    if (!p || p->dtype != ARCTOPK_F32 || !rank_mfma(p->r)) return ARCTOPK_EINVAL;
+    if (dtype != ARCTOPK_F32 && dtype != ARCTOPK_BF16) return ARCTOPK_EINVAL;
+    if (p->x_deferred || p->x_trail) return ARCTOPK_EINVAL;  // the caller finishes the plan's step first
+    p->sketch_op16 = dtype == ARCTOPK_BF16;
     return 0;
 }
 

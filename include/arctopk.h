@@ -1019,6 +1019,24 @@ int arctopk_decode_wire16_scatter(const arctopk_plan* plan, const void* packed_b
  * plan with a step deferred or trailing.  A plan without the binding runs the default step.
  */
 int arctopk_plan_bind_wire16(arctopk_plan* plan, void* packed_bf16);
+/*
+ * The operand type of the sketch projection of an ARCTOPK_F32 plan of rank 16 or 32 (not in the
+ * reference).  ARCTOPK_BF16: every later encode of the plan (arctopk_encode, arctopk_exchange_step,
+ * arctopk_step) rounds the two operands of P = X . V to bf16 -- b(): round to nearest even, NaN ->
+ * 0x7FC0 -- on their way into the matrix units:
+ *   sketch[row][j] = sum_c f(b(X[row][c])) * f(b(V[c][j]))
+ * with exact products, accumulated and stored in fp32 in the order of the fp32-operand encode (inside
+ * an MFMA the hardware's, k-groups ascending per wave, waves 0 .. 3, column parts ascending).  An
+ * eighth of the matrix instructions of the fp32 operands.  Only the sketch changes,
+ * which ranks the rows: X = G, G + E or G - E is formed in fp32 as before, EF14 stores E := X
+ * unrounded (bit for bit what the fp32 operands leave), RAW segments keep their unrounded values,
+ * keys mode forms the row key from the fp32 sums, and select, pack, decode and the wire never see
+ * the rounded operands.  ARCTOPK_F32 restores the default.  A plan made by arctopk_plan_group takes
+ * its parent's setting at that moment.  ARCTOPK_EINVAL, changing nothing, for a null plan, a plan
+ * that is not ARCTOPK_F32 (a bf16 plan's operands are bf16 already), r other than 16 or 32, another
+ * dtype, or a plan with a step deferred or trailing.  Host bookkeeping only: no device call.
+ */
+int arctopk_plan_set_sketch_operands(arctopk_plan* plan, int32_t dtype);
 
 /*
  * Device projections of one bucket call: for every SKETCH segment in bucket order,

@@ -7,9 +7,11 @@ call sits between two of the library's device-scope timed events; four disjoint 
 residual rotate, so no call finds its data in the Infinity Cache.  Per repetition: --warmup calls,
 then the median of --calls calls; the configurations alternate, --repeats repetitions each; the
 table gives the median and the min..max of the repetitions' medians.  Bytes are algorithmic: G and
-E read, E written (3 x the bucket) plus the sketch.
+E read, E written (3 x the bucket) plus the sketch.  "fp32/op16" rows: the fp32 bucket at r = 16 and
+32 with bf16 operands (arctopk_plan_set_sketch_operands), on the fp32 rows' buffers; their last
+column is the fp32-operand encode of the same rank in the same run over this one.
 
-    python scripts/bench_mfma_encode.py --out profiles/mfma_encode/table.txt
+    python scripts/bench_mfma_encode.py --out profiles/mfma_encode_bf16op/table.txt
 """
 import argparse
 import os
@@ -62,17 +64,22 @@ def main():
         for r in a.ranks:
             plan = BucketPlan(HEADLINE, r, 0.2, dtype, DEV)
             V = torch.randn(plan.info.v_len, device=DEV, generator=gen).to(dtype)
-            runs[name, r] = (plan, V, Gs, Es, NUMEL * 3 * Gs[0].element_size() + plan.info.sketch_len * Gs[0].element_size())
+            nbytes = NUMEL * 3 * Gs[0].element_size() + plan.info.sketch_len * Gs[0].element_size()
+            runs[name, r] = (plan, V, Gs, Es, nbytes)
+            if name == "fp32" and r in (16, 32):
+                op16 = BucketPlan(HEADLINE, r, 0.2, dtype, DEV)
+                N.check(N.lib().arctopk_plan_set_sketch_operands(op16.handle, N.BF16), "arctopk_plan_set_sketch_operands")
+                runs["fp32/op16", r] = (op16, V, Gs, Es, nbytes)
     med = {k: [] for k in runs}
     for _ in range(a.repeats):
         for k, (plan, V, Gs, Es, _) in runs.items():  # the configurations alternate
             med[k].append(median_us(lambda i: plan.encode(Gs[i % SETS], Es[i % SETS], N.EF14, True, V, stream),
                                     a.calls, a.warmup))
     lines = [f"encode, EF14 err_in 1, 16 x [2048, 2048]; median (min..max) of {a.repeats} repetitions' medians "
-             f"of {a.calls} calls", "dtype  r   us                        GB/s   vs r = 8"]
+             f"of {a.calls} calls", "dtype      r   us                        GB/s   vs r = 8 (op16: vs fp32 operands)"]
     for (name, r), m in med.items():
-        us, base = statistics.median(m), statistics.median(med[name, a.ranks[0]])
-        lines.append(f"{name:5s} {r:3d}  {us:7.1f} ({min(m):.1f}..{max(m):.1f})  {runs[name, r][4] / us / 1e3:7.0f}   "
+        us, base = statistics.median(m), statistics.median(med[("fp32", r) if name == "fp32/op16" else (name, a.ranks[0])])
+        lines.append(f"{name:9s} {r:3d}  {us:7.1f} ({min(m):.1f}..{max(m):.1f})  {runs[name, r][4] / us / 1e3:7.0f}   "
                      f"{base / us:.2f}x")
     text = "\n".join(lines)
     print(text)
